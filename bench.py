@@ -1,7 +1,13 @@
 """Ape-X DQN Pong benchmark: env-steps/s + learner updates/s on N MI355X (one process each).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1 under: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+ms_per_step, the configuration).  --dump-outputs DIR also writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs).  --full adds every other measurement below, each
+a run of its own after the timed region: the probe window's per-launch times and rooflines,
+the isolated kernels, the decoupled-actor sweep and the CPU baselines.
 
 Workload (BASELINE.json configs[1]): per GPU 256 vectorised actors on a
 synthetic Pong-shaped env (uint8 4x84x84 frame stacks, A = 6; ALE is not on the box), a 1 M
@@ -13,7 +19,7 @@ backward, Adam, priority write-back), all fp32 / fp64 as in the reference.  N > 
 scaling: every GPU runs the same per-GPU workload and the learner gradients are averaged
 with one RCCL all-reduce per update.
 
-The JSON line carries
+With --full the JSON line also carries
   roofline:        the dominant kernel of the step: whichever of conv2 / conv3 forward has the
                    most kernel time per iteration (conv_iteration_alone: its learner, target
                    and actor launches timed alone), measured in the learner's [s0; s1] pass
@@ -632,6 +638,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(dump_outputs; rank 0 writes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other measurement of the line: the probe window "
+                         "(live per-launch times, rooflines), the isolated kernels, the decoupled-actor sweep, the "
+                         "CPU baselines, the replica check at N > 1 (--probe-steps, --no-probe, --no-sweep, "
+                         "--no-cpu-baseline, --cpu-iters and --tag shape these; a plain run ignores them)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="pong",
                     help="pong (= pong-node) = BASELINE configs[1] at N = 1, configs[3] at N > 1 (256 actors and "
                          "1 M rows sharded over the N GPUs); pong-weak = configs[1] on every GPU; breakout = "
@@ -731,7 +745,9 @@ def main():
         from reth_amd import fused_learner
         fused_learner.HIP_WGRAD = None if args.wgrad == "miopen" else args.wgrad
     hip_conv = not args.miopen_conv
-    probe = hip_conv and not args.nchw and not args.eager and not args.no_probe
+    # the probe copies of the graphs are captured (and uploaded) only for --full's probe window; the
+    # timed region never replays them, and the dumped outputs are bit-identical with and without
+    probe = args.full and hip_conv and not args.nchw and not args.eager and not args.no_probe
     cfg = ApexConfig(n_actors=args.actors, capacity=args.capacity, batch_size=per_gpu_batch, num_actions=wl["actions"],
                      actor_steps_per_update=args.actor_steps_per_update, seed=0,
                      channels_last=not args.nchw, conv_benchmark=not args.no_conv_benchmark,
@@ -770,22 +786,6 @@ def main():
         ax.iteration()
         torch.cuda.synchronize()
 
-    # live per-launch timing (the probe window after the headline): HIP events on the launching
-    # stream around the launches the probe graph copies leave out -- conv2 / conv3 forward, the
-    # TD/heads backward and clip+Adam on the learner stream, the actor tail on the actor stream
-    # (ApexDQN._replay_parts / _learner_replay call conv_probe between the parts) -- and the
-    # replay shard's eager launches (ReplayKernelTimer)
-    conv_events = {"conv2": [], "conv3": []}
-
-    def conv_probe(tag):
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        base = tag[:-len("_end")] if tag.endswith("_end") else tag
-        ev = conv_events.setdefault(base, [])
-        if base == tag:
-            ev.append([e, None])
-        elif ev and ev[-1][1] is None:
-            ev[-1][1] = e
     spans = []
     if os.environ.get("RTH_BENCH_SPAN"):  # diagnostics: the learner block's span on its stream
         replay = ax._learner_replay
@@ -827,7 +827,10 @@ def main():
     debug = os.environ.get("RTH_BENCH_DEBUG")
     step_ev = [] if os.environ.get("RTH_BENCH_STEPTIMES") else None
     host_ms = []
+    last_learner = None
     for k in range(args.steps):
+        if args.dump_outputs and k == args.steps - 1 and ax._graphs is not None:
+            last_learner = ax._next_learner_variant()  # (a host-side read: which learner graph the last step replays)
         if k in win_at:
             e = torch.cuda.Event(enable_timing=True)
             e.record(ax._stream if hasattr(ax, "_stream") else None)
@@ -883,6 +886,136 @@ def main():
               file=sys.stderr, flush=True)
         print("host enqueue ms: " + " ".join(f"{h:.3f}" for h in host_ms), file=sys.stderr, flush=True)
     win_ms = [a[1].elapsed_time(b[1]) / (b[0] - a[0]) for a, b in zip(win_ev, win_ev[1:])]
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs on the device
+        dumped = dump_outputs(args.dump_outputs, ax, last_learner)
+    # everything below the headline is --full's (collective legs on every rank, the line on rank 0)
+    full = full_measurements(args, ax, cfg, dev, rank, world, probe) if args.full else None
+    if rank != 0:  # rank 0 only assembles and prints the line
+        if world > 1:
+            shutdown(ax)  # graphs released, then the process group destroyed (reth_amd.dist)
+        return
+    f = qnet_flops_per_sample(cfg.num_actions)
+    flops_update = 5 * cfg.batch_size * f  # online fwd on s0 + s1, target fwd on s1, bwd (~2 fwd)
+    # actors: the acting stacks (N) -- the rows' heads come from the per-stack cache
+    # (VecActors.step_fused dedup mode; the terminal stacks of ended episodes, ~N/2000 per
+    # step, and the full passes after a weights reload are not counted)
+    flops_actor = cfg.n_actors * f * args.actor_steps_per_update
+    flops_step = flops_update + flops_actor
+    step_s = dt / args.steps
+    out = {
+        "metric": "env-steps/sec + learner updates/sec, Ape-X DQN Pong, 1/2/4/8 MI355X",
+        "value": round(n_env / dt, 1),
+        "unit": "env-steps/s",
+        "learner_updates_per_sec": round(n_upd / dt, 2),
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_s * 1e3, 3),
+        "ms_per_step_windows": [round(w, 4) for w in win_ms],
+        "ms_per_step_window_median": round(float(np.median(win_ms)), 4) if win_ms else None,
+        "graph_prepare": dict(prep, note="setup before the W warmup steps: the capture iterations, hipGraphUpload of "
+                                         "every captured graph, then `settle` untimed iterations of the captured loop "
+                                         "(synchronized every 8th and the last 16; each warmup step synchronized: the "
+                                         "host never enters the timed region's first sync far ahead of the GPU)"),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": ("synthetic (Philox uint8 Pong-shaped frames, random-init Q-net; no ALE/checkpoints on the box)"
+                 if args.env == "synthetic" else
+                 "synthetic raw 210x160x3 screens (Philox%s) through the device Atari preprocessing, random-init Q-net; "
+                 "no ALE/checkpoints on the box" % (", copied host -> device from pinned memory every step"
+                                                     if args.env == "atari-h2d" else " on the device")),
+        "config": {"workload": (wl["name_node"].format(n=world) if shard else wl["name"]),
+                   "baseline_config": ("configs[3]" if shard else {"pong": "configs[1]", "pong-node": "configs[1]",
+                                                                   "pong-weak": "configs[1]" if world == 1 else
+                                                                   "configs[1] x N (weak)",
+                                                                   "breakout": "configs[2]"}[args.workload]),
+                   "actors_per_gpu": cfg.n_actors, "actors_total": cfg.n_actors * world,
+                   "replay_capacity_total": cfg.capacity * world, "num_actions": cfg.num_actions,
+                   "replay_capacity_per_gpu": cfg.capacity, "replay_prefilled": True, "batch_size": cfg.batch_size,
+                   "n_step": cfg.n_step, "alpha": cfg.alpha, "beta": cfg.beta,
+                   "actor_steps_per_update": cfg.actor_steps_per_update, "env": cfg.env,
+                   "replay_storage": replay_storage(ax),
+                   "qnet_layout": "channels_last" if cfg.channels_last else "nchw",
+                   "conv_benchmark": cfg.conv_benchmark, "hip_graph": cfg.hip_graph, "hip_conv": cfg.hip_conv,
+                   "global_batch": cfg.batch_size * world,
+                   "batch_mode": "hyperparameter-faithful (global batch split over the learners)" if args.faithful
+                                 else "throughput (B per GPU)",
+                   "parallelism": (f"dp{world} learner (RCCL grad all-reduce) + {world} replay shards" if world > 1
+                                   else "one GPU: actors, replay shard and learner")},
+        "dist": {"world": world, "backend": backend, "rccl": backend == "nccl",
+                 "replicas_identical": full["replicas_identical"] if full else None} if world > 1 else None,
+        "qnet_mfma": {"tflops_per_step": round(flops_step / 1e12, 4),
+                      "achieved_tflops": round(flops_step / step_s / 1e12, 2),
+                      "peak_fp32_tflops": FP32_PEAK_TFLOPS},
+        "full": bool(args.full),
+        "outputs_dumped": dumped,
+    }
+    if full:
+        del full["replicas_identical"]
+        out.update(full)
+    print(json.dumps(out), flush=True)
+    if world > 1:
+        shutdown(ax)
+
+
+def dump_outputs(path, ax, last_learner):
+    """--dump-outputs: what the last timed step left for its caller, as path/<name>.npy
+    (float32, or float64 where the device holds fp64 / int64); returns {name: shape}.
+      q_network_params       every online Q-network parameter after the step's Adam update,
+                             flattened in state_dict order
+      learner_abs_td         |td| of the step's batch, the new priorities (graph replay only:
+                             the output of the learner graph `last_learner` the step replayed)
+      learner_batch_indices, learner_is_weights
+                             the PER sample the step's update consumed
+      actor_actions, actor_rewards, actor_dones
+                             the vectorised actors' last env step
+    The run is seeded (ApexConfig.seed, the prefill's generator, the device Philox streams), so
+    the same arguments give the same inputs run after run."""
+    torch.cuda.synchronize()
+    arrays = {"q_network_params": torch.cat([v.detach().reshape(-1).float()
+                                             for v in ax.solver.q_network.state_dict().values()])}
+    if last_learner is not None:
+        arrays["learner_abs_td"] = ax._graphs["learn_td"][last_learner]
+        _, idx, isw = ax.loader._slots[last_learner[1]]
+        arrays["learner_batch_indices"], arrays["learner_is_weights"] = idx, isw
+    act = ax.actors
+    arrays.update(actor_actions=act.action, actor_rewards=act.reward, actor_dones=act.done)
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.itemsize <= 4 and a.dtype.kind in "fbui" else np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def full_measurements(args, ax, cfg, dev, rank, world, probe):
+    """--full: the measurements after the timed region, each a run of its own -- the probe
+    window, the isolated gather / conv launches, the decoupled-actor sweep, the replica check,
+    the CPU baselines.  Every rank runs the collective legs; returns the extra fields of the
+    line on rank 0 (None elsewhere)."""
+    import torch.distributed as dist
+
+    # live per-launch timing (the probe window after the headline): HIP events on the launching
+    # stream around the launches the probe graph copies leave out -- conv2 / conv3 forward, the
+    # TD/heads backward and clip+Adam on the learner stream, the actor tail on the actor stream
+    # (ApexDQN._replay_parts / _learner_replay call conv_probe between the parts) -- and the
+    # replay shard's eager launches (ReplayKernelTimer)
+    conv_events = {"conv2": [], "conv3": []}
+
+    def conv_probe(tag):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        base = tag[:-len("_end")] if tag.endswith("_end") else tag
+        ev = conv_events.setdefault(base, [])
+        if base == tag:
+            ev.append([e, None])
+        elif ev and ev[-1][1] is None:
+            ev[-1][1] = e
     # ------------------------------------------------------------------ the probe window
     # after the headline: the probe graph copies replay with HIP events around the timed
     # launches, and the replay shard's launches are timed by ReplayKernelTimer
@@ -938,23 +1071,13 @@ def main():
     decoupled = None
     if not args.no_sweep and ax._graphs is not None:
         decoupled = decoupled_actors(ax, dev, world)
-    if rank != 0:  # no collective after this point (rank 0 only assembles and prints the line)
-        if world > 1:
-            shutdown(ax)  # graphs released, then the process group destroyed (reth_amd.dist)
-        return
+    if rank != 0:  # no collective after this point
+        return None
     cpu = None
     if not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(n_actors=cfg.n_actors, batch=cfg.batch_size, iters=args.cpu_iters)
         cpu["reference_actor_layout"] = cpu_actor_baseline(usable_cores()[0])
-    f = qnet_flops_per_sample(cfg.num_actions)
-    flops_update = 5 * cfg.batch_size * f  # online fwd on s0 + s1, target fwd on s1, bwd (~2 fwd)
-    # actors: the acting stacks (N) -- the rows' heads come from the per-stack cache
-    # (VecActors.step_fused dedup mode; the terminal stacks of ended episodes, ~N/2000 per
-    # step, and the full passes after a weights reload are not counted)
-    flops_actor = cfg.n_actors * f * args.actor_steps_per_update
-    flops_step = flops_update + flops_actor
-    step_s = dt / args.steps
-    tsig = traffic_signature(world, cfg, fids)
+    tsig =traffic_signature(world, cfg, fids)
     tprof, tsrc, treason = load_traffic_file(args.tag, tsig)
     traffic, traffic_src, traffic_null = traffic_field(tprof, tsrc, treason, "gather_hbm_bytes_per_launch")
     c2_traffic, c2_src, c2_null = traffic_field(tprof, tsrc, treason, "conv2_learner_hbm_bytes_per_launch")
@@ -1012,70 +1135,22 @@ def main():
             else roofline_conv2
     elif roofline_conv3:
         roofline = roofline_conv3
-    out = {
-        "metric": "env-steps/sec + learner updates/sec, Ape-X DQN Pong, 1/2/4/8 MI355X",
-        "value": round(n_env / dt, 1),
-        "unit": "env-steps/s",
-        "learner_updates_per_sec": round(n_upd / dt, 2),
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(step_s * 1e3, 3),
-        "ms_per_step_windows": [round(w, 4) for w in win_ms],
-        "ms_per_step_window_median": round(float(np.median(win_ms)), 4) if win_ms else None,
-        "graph_prepare": dict(prep, note="setup before the W warmup steps: the capture iterations, hipGraphUpload of "
-                                         "every captured graph, then `settle` untimed iterations of the captured loop "
-                                         "(synchronized every 8th and the last 16; each warmup step synchronized: the "
-                                         "host never enters the timed region's first sync far ahead of the GPU)"),
-        "probe_window": {"steps": probe_steps, "ms_per_step": round(probe_ms_per_step, 4) if probe_ms_per_step else None,
+    return {
+        "replicas_identical": replicas,
+        "probe_window":{"steps": probe_steps, "ms_per_step": round(probe_ms_per_step, 4) if probe_ms_per_step else None,
                          "note": "after the timed region: the probe graph copies (cut at the timed launches) + the "
                                  "replay shard's launch timers; every per-launch time in this line comes from it"},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": ("synthetic (Philox uint8 Pong-shaped frames, random-init Q-net; no ALE/checkpoints on the box)"
-                 if args.env == "synthetic" else
-                 "synthetic raw 210x160x3 screens (Philox%s) through the device Atari preprocessing, random-init Q-net; "
-                 "no ALE/checkpoints on the box" % (", copied host -> device from pinned memory every step"
-                                                     if args.env == "atari-h2d" else " on the device")),
-        "config": {"workload": (wl["name_node"].format(n=world) if shard else wl["name"]),
-                   "baseline_config": ("configs[3]" if shard else {"pong": "configs[1]", "pong-node": "configs[1]",
-                                                                   "pong-weak": "configs[1]" if world == 1 else
-                                                                   "configs[1] x N (weak)",
-                                                                   "breakout": "configs[2]"}[args.workload]),
-                   "actors_per_gpu": cfg.n_actors, "actors_total": cfg.n_actors * world,
-                   "replay_capacity_total": cfg.capacity * world, "num_actions": cfg.num_actions,
-                   "replay_capacity_per_gpu": cfg.capacity, "replay_prefilled": True, "batch_size": cfg.batch_size,
-                   "n_step": cfg.n_step, "alpha": cfg.alpha, "beta": cfg.beta,
-                   "actor_steps_per_update": cfg.actor_steps_per_update, "env": cfg.env,
-                   "replay_storage": replay_storage(ax),
-                   "qnet_layout": "channels_last" if cfg.channels_last else "nchw",
-                   "conv_benchmark": cfg.conv_benchmark, "hip_graph": cfg.hip_graph, "hip_conv": cfg.hip_conv,
-                   "global_batch": cfg.batch_size * world,
-                   "batch_mode": "hyperparameter-faithful (global batch split over the learners)" if args.faithful
-                                 else "throughput (B per GPU)",
-                   "parallelism": (f"dp{world} learner (RCCL grad all-reduce) + {world} replay shards" if world > 1
-                                   else "one GPU: actors, replay shard and learner")},
-        "dist": {"world": world, "backend": backend, "rccl": backend == "nccl",
-                 "replicas_identical": replicas} if world > 1 else None,
         "roofline": roofline,
         "roofline_gather": roofline_gather,
         "roofline_conv2": roofline_conv2,
         "roofline_conv3": roofline_conv3,
         "conv_iteration_alone": conv_alone,
-        "qnet_mfma": {"tflops_per_step": round(flops_step / 1e12, 4),
-                      "achieved_tflops": round(flops_step / step_s / 1e12, 2),
-                      "peak_fp32_tflops": FP32_PEAK_TFLOPS},
         "roofline_conv1": conv1,
         "roofline_hbm": hbm_rooflines(ax, ktimer, conv_ms, tprof, tsrc, treason),
         "traffic_measured_on": tprof.get("measured_on") if tprof else None,
         "decoupled_actors": decoupled,
         "cpu_baseline": cpu,
     }
-    print(json.dumps(out), flush=True)
-    if world > 1:
-        shutdown(ax)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ rounds=$1 steps=$2; shift 2
 for r in $(seq 1 "$rounds"); do
   for spec in "$@"; do
     name=${spec%%:*} envs=${spec#*:}
-    env $envs timeout -k 10 300 python bench.py --steps "$steps" --warmup 30 --no-cpu-baseline --no-sweep \
+    env $envs timeout -k 10 300 python bench.py --full --steps "$steps" --warmup 30 --no-cpu-baseline --no-sweep \
       > "gpurun_out/abe_${name}_$r.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$name round $r failed rc=$rc"; tail -5 "gpurun_out/abe_${name}_$r.log"; exit $rc; fi

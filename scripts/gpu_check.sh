@@ -16,8 +16,8 @@ for step in "$@"; do
   case "$step" in
     tests) run pytest_gpu 1200 python -m pytest tests -m gpu -q -rf ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py ;;
-    benchq) run bench_quick 600 python bench.py --steps 50 --warmup 10 --cpu-iters 5 ;;
+    bench) run bench 900 python bench.py --full ;;
+    benchq) run bench_quick 600 python bench.py --full --steps 50 --warmup 10 --cpu-iters 5 ;;
     variants)
       run bench_nchw 600 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --nchw
       run bench_cl 600 python bench.py --steps 100 --warmup 20 --no-cpu-baseline
@@ -82,7 +82,7 @@ for step in "$@"; do
     # the evidence set for a round: the bench line, its rocprof kernel trace + stats, and the two
     # PMC passes of the same command (scripts/summarize_profile.py TAG --steps 200 reads them)
     evidence) export TMPDIR=/tmp
-         run bench_evidence 900 python bench.py &&
+         run bench_evidence 900 python bench.py --full &&
          run rocprof_stats 900 rocprofv3 --kernel-trace --stats --output-format csv \
             -d "$PWD/gpurun_out/prof" -o run -- python bench.py --steps 200 --warmup 20 --no-cpu-baseline &&
          run pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv --kernel-include-regex "rth::" \
