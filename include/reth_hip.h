@@ -590,6 +590,25 @@ int rth_fc_f32_supported(int64_t M, int64_t N, int64_t K);
 int64_t rth_fc_f32_workspace(int64_t M, int64_t N, int64_t K);
 int rth_fc_f32(const float *x_dev, int64_t ldx, int64_t M, const float *w_dev, int64_t N, int64_t K,
                const float *bias_dev, int32_t relu, float *y_dev, void *workspace_dev, void *stream);
+/* FC1's backward (r07; the backward of dqn_model.py:38-47, the first Linear of both branches as
+ * one [N, K] weight, under dqn_solver.py:116-117 loss.backward()) on the exact-split bf16 MFMA,
+ * both gradients in one launch: gx [B, K] = gy w and gw [N, K] = gy^T x, from gy [B, N] (the
+ * gradient of the Linear's output, already ReLU-masked; row-major, row stride ldg), x [B, K] (the
+ * Linear's input; row-major, row stride ldx) and w [N, K] (row-major, contiguous); gx and gw are
+ * written contiguous, every element, with no zero fill expected.  gx_dev and gw_dev are each
+ * nullable: a NULL gradient is not computed and its operand (w for gx, x for gw) may be NULL;
+ * both NULL is an error; a gradient's bits do not depend on whether the other is asked for.
+ * B % 64 == 0, N % 128 == 0, K % 64 == 0 (rth_fc_bwd_supported); strides multiples of 4 floats,
+ * buffers 16-byte aligned.  The tiles and the k splits are fixed functions of (B, N, K), so
+ * rth_fc_bwd_workspace (bytes; 0 where nothing is split, then workspace_dev may be NULL) is too;
+ * the workspace needs no initialisation.  No atomics: fixed-order split partials and one reduce
+ * launch, run-to-run bit-identical.  Launches on one stream are ordered; two calls sharing a
+ * workspace on two streams are not (as rth_conv_dgrad_ws).  Replaces the two hipBLASLt GEMMs of
+ * the learner's FC1 backward where model.FC1_BWD = "hip". */
+int rth_fc_bwd_supported(int64_t B, int64_t N, int64_t K);
+int64_t rth_fc_bwd_workspace(int64_t B, int64_t N, int64_t K);
+int rth_fc_bwd(const float *gy_dev, int64_t ldg, const float *x_dev, int64_t ldx, const float *w_dev, int64_t B,
+               int64_t N, int64_t K, float *gx_dev, float *gw_dev, void *workspace_dev, void *stream);
 int rth_conv_dgrad_ws(const rth_conv_shape *shape, const float *gy_dev, int64_t n, const float *w_ohwi_dev,
                       float *gx_dev, void *workspace_dev, void *stream);
 /* Weight gradient of conv2d(x, w) for the fp32 channels-last layers (conv2 and conv3 of the

@@ -199,6 +199,9 @@ SIGNATURES = {
     "rth_fc_f32_supported": (c_i32, [c_i64, c_i64, c_i64]),
     "rth_fc_f32_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "rth_fc_f32": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "rth_fc_bwd_supported": (c_i32, [c_i64, c_i64, c_i64]),
+    "rth_fc_bwd_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "rth_fc_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rth_conv_dgrad_ws": (c_i32, [ctypes.POINTER(ConvShape), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rth_conv_dgrad_prepacked": (c_i32, [ctypes.POINTER(ConvShape), c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rth_conv_dgrad_relu_supported": (c_i32, [ctypes.POINTER(ConvShape)]),

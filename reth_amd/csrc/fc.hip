@@ -623,11 +623,276 @@ static int fcf_splits(int M, int N, int K) {
   return s < chunks ? s : chunks;
 }
 
+// FC1's backward (r07): gx [B, K] = gy w and gw [N, K] = gy^T x on the same exact-split bf16 MFMA
+// (nine MFMAs per 32-deep chunk in fc_ta / fc_tb order, chunks in order, splits reduced in order).
+// Workgroup = 4 waves over a (32 MB) x 64 output tile -- wave (wm, wn): MB row blocks x 2 column
+// blocks of 16 x 16 -- and one split of the 32-deep reduction chunks; both operands of a chunk
+// are split once per workgroup into k_fc_x9t's LDS fragment order (unit (block, term, lane):
+// the 8 reduction values 8 g .. 8 g + 7 of row / column r of the block, lane = r + 16 g),
+// double-buffered, one barrier per chunk, the next chunk's global loads in flight in registers.
+// What differs from the forward is where the reduction index lies in memory:
+//   A along the reduction (the data gradient's gy [B, N], summed over n): a thread stages 16
+//     consecutive reduction values of one row, four 16-byte loads (k_fc_x9t's staging);
+//   A or B across the reduction (w [N, K] summed over n; gy [B, N] and x [B, K] summed over the
+//     batch row): the contiguous direction is the output's, so a thread takes ONE output index
+//     and loads its 8 reduction values 8 g .. 8 g + 7 as 8 dwords a row stride apart -- the 64
+//     lanes of a wave read 256 contiguous bytes of each row -- which is one fragment unit: the
+//     transpose happens in the choice of what a thread loads, consecutive lanes write
+//     consecutive units (no bank conflict), and every value is still split once.
+// 36 KB of LDS per buffer (A 8 blocks, B 4), 72 KB per workgroup: two workgroups per CU.
+constexpr int kFwTn = 64, kFwThreads = 256;
+constexpr int kFwAUnits = 8 * 3 * 64, kFwUnits = kFwAUnits + 4 * 3 * 64;  // 16-byte units of one buffer
+template <bool AT, int MB>  // AT: A is read across the reduction, A(m, r) = a[r lda + m]; else a[m lda + r]
+__device__ __forceinline__ void fc_bwd_tile(uint4 (*sl)[kFwUnits], const float *__restrict__ a, int64_t lda,
+                                            const float *__restrict__ b, int64_t ldb, float *__restrict__ out,
+                                            int64_t ldo, int m0, int n0, int c0, int c1) {
+  constexpr int TM = 32 * MB, T = kFwThreads, NR = 2;
+  constexpr int ATASKS = AT ? 4 * TM : 2 * TM, AJ = (ATASKS + T - 1) / T;  // A staging tasks, per thread
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, r = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave & 1, wn = wave >> 1;
+  // A task u = tid + j T (whole waves past ATASKS idle): along the reduction, row u % TM, values
+  // 16 (u / TM) .. + 15 of the chunk; across it, row u % TM, values 8 (u / TM) .. + 7
+  const float *asrc[AJ];
+#pragma unroll
+  for (int j = 0; j < AJ; ++j) {
+    const int u = tid + j * T, rr = u % TM, h = u / TM;
+    asrc[j] = AT ? a + (int64_t)(8 * h) * lda + m0 + rr : a + (int64_t)(m0 + rr) * lda + 16 * h;
+  }
+  // B task: column tid & 63, values 8 (tid >> 6) .. + 7 of the chunk
+  const float *bsrc = b + (int64_t)(8 * (tid >> 6)) * ldb + n0 + (tid & 63);
+  f32x4 ra4[NR][AJ][4];  // A along the reduction
+  float ra1[NR][AJ][8];  // A across it
+  float rb[NR][8];
+  auto load = [&](int c, int s) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < AJ; ++j)
+      if (tid + j * T < ATASKS) {
+        if constexpr (AT) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) ra1[s][j][q] = asrc[j][(int64_t)(32 * c + q) * lda];
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ra4[s][j][q] = *reinterpret_cast<const f32x4 *>(asrc[j] + 32 * c + 4 * q);
+        }
+      }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) rb[s][q] = bsrc[(int64_t)(32 * c + q) * ldb];
+  };
+  auto put = [&](const float (&v)[8], uint4 *dst) __attribute__((always_inline)) {  // dst: the unit of term 0
+    bf16x8 tr[3];
+    split3_pk8(v, tr);
+#pragma unroll
+    for (int t = 0; t < 3; ++t) dst[t * 64] = __builtin_bit_cast(uint4, tr[t]);
+  };
+  auto stage = [&](int s, uint4 *buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < AJ; ++j)
+      if (tid + j * T < ATASKS) {
+        const int u = tid + j * T, rr = u % TM, h = u / TM;
+        uint4 *blk = buf + (rr >> 4) * 3 * 64 + (rr & 15);
+        if constexpr (AT) {
+          put(ra1[s][j], blk + 16 * h);
+        } else {
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            const f32x4 lo = ra4[s][j][2 * hh], hi = ra4[s][j][2 * hh + 1];
+            const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            put(v, blk + 16 * (2 * h + hh));
+          }
+        }
+      }
+    const int col = tid & 63;
+    put(rb[s], buf + kFwAUnits + (col >> 4) * 3 * 64 + (col & 15) + 16 * (tid >> 6));
+  };
+  // two accumulators per output: the leading term (1,1) in acc, the eight smaller ones (at most
+  // 2^-8 of it) in lo, added once at the end -- the reduction here is one chain of up to 16
+  // chunks, and with all nine terms in one accumulator six of the nine MFMAs per chunk each round
+  // the full sum (measured at 512 x 512 x 3136: 2.9e-6 from fp64 against this form's figure in
+  // profiles/r07/fc1_bwd.txt); lo's roundings are 2^-8 of that
+  f32x4 acc[MB][2], lo[MB][2];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = lo[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto compute = [&](const uint4 *buf) __attribute__((always_inline)) {
+    bf16x8 af[MB][3], bfr[2][3];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) af[mb][t] = __builtin_bit_cast(bf16x8, buf[((MB * wm + mb) * 3 + t) * 64 + lane]);
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        bfr[nb][t] = __builtin_bit_cast(bf16x8, buf[kFwAUnits + ((2 * wn + nb) * 3 + t) * 64 + lane]);
+    // term-major, as k_fc_x9t: the 9 terms in fc_ta / fc_tb order, the first eight into lo
+    static_assert(fc_ta(8) == 0 && fc_tb(8) == 0, "the leading term is the last");
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          f32x4 &d = k < 8 ? lo[mb][nb] : acc[mb][nb];
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mb][fc_ta(k)], bfr[nb][fc_tb(k)], d, 0, 0, 0);
+        }
+  };
+  // k_fc_x9t's pipeline with one chunk in flight: chunk c0 + i's MFMAs from buffer i & 1, chunk
+  // i + 1 staged from ring set (i + 1) & 1 into the other buffer, chunk i + 3 loaded into that
+  // set (past c1 - 1 the loads repeat the range's last chunk: in bounds, unused)
+  auto clampc = [&](int c) { return c < c1 ? c : c1 - 1; };
+  load(c0, 0);
+  load(clampc(c0 + 1), 1);
+  stage(0, sl[0]);
+  load(clampc(c0 + 2), 0);
+  __syncthreads();
+  auto iter = [&](int i, auto is) __attribute__((always_inline)) {
+    constexpr int s = decltype(is)::value;  // i & 1
+    compute(sl[s]);
+    stage(s ^ 1, sl[s ^ 1]);
+    load(clampc(c0 + i + 3), s ^ 1);
+    __syncthreads();
+  };
+  const int n_it = c1 - c0;
+  int i = 0;
+  for (; i + 2 <= n_it; i += 2) {
+    iter(i, std::integral_constant<int, 0>{});
+    iter(i + 1, std::integral_constant<int, 1>{});
+  }
+  if (i < n_it) iter(i, std::integral_constant<int, 0>{});
+  // D: lane holds rows 4 g + e of each 16-row block, column r of each 16-column block
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        out[(int64_t)(m0 + 16 * (MB * wm + mb) + 4 * g + e) * ldo + n0 + 16 * (2 * wn + nb) + r] =
+            radd(acc[mb][nb][e], lo[mb][nb][e]);
+}
+
+// both gradients in one launch: blocks [0, nblk_d) = the data gradient's (tile, split) pairs,
+// rows in tiles of 32 MBD, the rest the weight gradient's (128-row tiles of N); an output not
+// asked for has no blocks.  gx_out / gw_out: the output, or its split partials [splits][rows][K]
+template <int MBD>
+__global__ __launch_bounds__(kFwThreads) void k_fc_bwd(const float *__restrict__ gy, int64_t ldg,
+                                                       const float *__restrict__ x, int64_t ldx,
+                                                       const float *__restrict__ w, int B, int N, int K,
+                                                       float *__restrict__ gx_out, float *__restrict__ gw_out,
+                                                       int nblk_d, int sd, int sw) {
+  __shared__ uint4 sl[2][kFwUnits];
+  const int tiles_k = K / kFwTn;
+  int blk = (int)blockIdx.x;
+  if (blk < nblk_d) {
+    const int tile = blk / sd, split = blk % sd, chunks = N / 32;
+    fc_bwd_tile<false, MBD>(sl, gy, ldg, w, K, gx_out + (int64_t)split * B * K, K, (tile / tiles_k) * 32 * MBD,
+                            (tile % tiles_k) * kFwTn, chunks * split / sd, chunks * (split + 1) / sd);
+  } else {
+    blk -= nblk_d;
+    const int tile = blk / sw, split = blk % sw, chunks = B / 32;
+    fc_bwd_tile<true, 4>(sl, gy, ldg, x, ldx, gw_out + (int64_t)split * N * K, K, (tile / tiles_k) * 128,
+                         (tile % tiles_k) * kFwTn, chunks * split / sw, chunks * (split + 1) / sw);
+  }
+}
+
+// the split partials of both gradients summed in split order (fc_reduce_wg, no bias, no
+// activation) in one launch: blocks [0, nred_d) the data gradient's, the rest the weight gradient's
+template <int MAXS>
+__global__ __launch_bounds__(256) void k_fc_bwd_reduce(const float *__restrict__ pd, int sd, int64_t MNd,
+                                                       float *__restrict__ gx, int nred_d,
+                                                       const float *__restrict__ pw, int sw, int64_t MNw,
+                                                       float *__restrict__ gw, int K) {
+  if ((int)blockIdx.x < nred_d)
+    fc_reduce_wg<MAXS>((int)blockIdx.x, pd, sd, MNd, K, nullptr, 0, gx, K);
+  else
+    fc_reduce_wg<MAXS>((int)blockIdx.x - nred_d, pw, sw, MNw, K, nullptr, 0, gw, K);
+}
+
+// the backward's plan, a fixed function of (B, N, K): the data gradient's row tile (128 where
+// B % 128 == 0, else 64) and each gradient's k splits -- doubled while the gradient's workgroups
+// stay within one round of 256 CUs and every split keeps at least 2 chunks, at most 8.  The
+// loop's B = 512: 196 + 196 tiles, no split, no reduce launch; B = 64: 49 tiles x 4 splits + 196.
+constexpr int kFwMaxSplits = 8;
+struct FcBwdPlan {
+  int mbd, tiles_d, sd, tiles_w, sw;
+};
+static FcBwdPlan fc_bwd_plan(int B, int N, int K) {
+  auto splits = [](int tiles, int chunks) {
+    int s = 1;
+    while (2 * s * tiles <= 256 && 4 * s <= chunks && 2 * s <= kFwMaxSplits) s *= 2;
+    return s;
+  };
+  FcBwdPlan p;
+  p.mbd = B % 128 == 0 ? 4 : 2;
+  p.tiles_d = (B / (32 * p.mbd)) * (K / kFwTn);
+  p.sd = splits(p.tiles_d, N / 32);
+  p.tiles_w = (N / 128) * (K / kFwTn);
+  p.sw = splits(p.tiles_w, B / 32);
+  return p;
+}
+
 }  // namespace rth
 
 using namespace rth;
 
 extern "C" {
+
+int rth_fc_bwd_supported(int64_t B, int64_t N, int64_t K) {
+  return B > 0 && B % 64 == 0 && N > 0 && N % 128 == 0 && K > 0 && K % kFwTn == 0 && B * K < (1ll << 31) &&
+                 N * K < (1ll << 31) && B * N < (1ll << 31)
+             ? 1
+             : 0;
+}
+
+int64_t rth_fc_bwd_workspace(int64_t B, int64_t N, int64_t K) {
+  if (!rth_fc_bwd_supported(B, N, K)) return 0;
+  const FcBwdPlan p = fc_bwd_plan((int)B, (int)N, (int)K);
+  return (p.sd > 1 ? (int64_t)p.sd * B * K * 4 : 0) + (p.sw > 1 ? (int64_t)p.sw * N * K * 4 : 0);
+}
+
+int rth_fc_bwd(const float *gy, int64_t ldg, const float *x, int64_t ldx, const float *w, int64_t B, int64_t N,
+               int64_t K, float *gx, float *gw, void *workspace, void *stream) {
+  RTH_REQUIRE(gy && (gx || gw), "rth_fc_bwd: NULL gy, or neither gradient asked for");
+  RTH_REQUIRE((!gx || w) && (!gw || x), "rth_fc_bwd: NULL operand of a gradient asked for");
+  RTH_REQUIRE(rth_fc_bwd_supported(B, N, K), "rth_fc_bwd: shape %lld x %lld x %lld not built (B %% 64, N %% 128, K %% 64)",
+              (long long)B, (long long)N, (long long)K);
+  RTH_REQUIRE(ldg >= N && ldg % 4 == 0 && (!gw || (ldx >= K && ldx % 4 == 0)) && (B - 1) * ldg + N < (1ll << 31) &&
+                  (!gw || (B - 1) * ldx + K < (1ll << 31)),
+              "rth_fc_bwd: row strides %lld, %lld", (long long)ldg, (long long)ldx);
+  RTH_REQUIRE(((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) |
+                reinterpret_cast<uintptr_t>(gx) | reinterpret_cast<uintptr_t>(gw)) &
+               15) == 0,
+              "rth_fc_bwd: misaligned buffer");
+  const FcBwdPlan p = fc_bwd_plan((int)B, (int)N, (int)K);
+  const int sd = gx ? p.sd : 1, sw = gw ? p.sw : 1;
+  RTH_REQUIRE((sd == 1 && sw == 1) || (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+              "rth_fc_bwd: %d / %d splits need the workspace (rth_fc_bwd_workspace)", sd, sw);
+  hipStream_t s = as_stream(stream);
+  // the partials' places in the workspace do not depend on which gradients are asked for
+  float *pd = static_cast<float *>(workspace);
+  float *pw = pd ? pd + (p.sd > 1 ? (int64_t)p.sd * B * K : 0) : nullptr;
+  float *od = sd > 1 ? pd : gx, *ow = sw > 1 ? pw : gw;
+  const int nblk_d = gx ? p.tiles_d * sd : 0, nblk_w = gw ? p.tiles_w * sw : 0;
+  const dim3 grid((unsigned)(nblk_d + nblk_w));
+  if (p.mbd == 4)
+    hipLaunchKernelGGL(k_fc_bwd<4>, grid, dim3(kFwThreads), 0, s, gy, ldg, x, ldx, w, (int)B, (int)N, (int)K, od, ow,
+                       nblk_d, sd, sw);
+  else
+    hipLaunchKernelGGL(k_fc_bwd<2>, grid, dim3(kFwThreads), 0, s, gy, ldg, x, ldx, w, (int)B, (int)N, (int)K, od, ow,
+                       nblk_d, sd, sw);
+  RTH_LAUNCHED();
+  if (sd > 1 || sw > 1) {
+    const int64_t MNd = B * K, MNw = N * K;
+    const int nred_d = sd > 1 ? (int)((MNd / 4 + 255) / 256) : 0, nred_w = sw > 1 ? (int)((MNw / 4 + 255) / 256) : 0;
+    const dim3 rgrid((unsigned)(nred_d + nred_w));
+    if (sd <= 4 && sw <= 4)
+      hipLaunchKernelGGL(k_fc_bwd_reduce<4>, rgrid, dim3(256), 0, s, pd, sd, MNd, gx, nred_d, pw, sw, MNw, gw, (int)K);
+    else
+      hipLaunchKernelGGL(k_fc_bwd_reduce<8>, rgrid, dim3(256), 0, s, pd, sd, MNd, gx, nred_d, pw, sw, MNw, gw, (int)K);
+    RTH_LAUNCHED();
+  }
+  return RTH_OK;
+}
 
 int rth_fc_x9_supported(int64_t M, int64_t N, int64_t K) {
   return M > 0 && M % kFcTm == 0 && N > 0 && N % kFcTn == 0 && K >= 32 && K % 32 == 0 && M * K < (1ll << 31) &&

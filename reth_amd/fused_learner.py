@@ -13,7 +13,8 @@ path of solver.py (compute_grads with torch.autograd), without the autograd engi
   TD        rth_td_huber on the raw heads -> |td|, loss, d(loss)/d(heads of s0), fused with
   backward  FC2 + threshold + both bias sums (rth_td_heads_backward_branches: FC2's
             gradients written in branch form; also the Trainer's mean |td|), FC1 as two
-            GEMMs (its branch gradients are row slices of the merged ones), conv3 as
+            GEMMs (its branch gradients are row slices of the merged ones; hipBLASLt's, or
+            with model.FC1_BWD = "hip" both in one rth_fc_bwd launch), conv3 as
             rth_relu_bias_grad_nchw + MIOpen's data and weight gradients, conv2 as
             rth_relu_bias_grad + rth_conv_dgrad + MIOpen's weight gradient, conv1 as
             rth_conv_relu_wgrad straight from the uint8 stacks (f32 input:
@@ -61,7 +62,10 @@ def _net_workspace(net, kind, shape, device):
     """a backward kernel's workspace, owned by the network: two learners in one process may
     run (or replay) their backward passes on different streams, so no workspace is shared
     between them -- rth_conv_dgrad_ws's packed flipped kernel, rth_conv_wgrad_{f32,x9}'s
-    split partials, rth_conv_relu_wgrad's conv1 partials"""
+    split partials, rth_conv_relu_wgrad's conv1 partials; kind "fc1_bwd" (shape = (B, N, K)):
+    rth_fc_bwd's split partials, keyed by (device, B, N, K)"""
+    if kind == "fc1_bwd":
+        return model.fc1_bwd_workspace(net, device, *shape)
     cache = net.__dict__.setdefault("_bwd_ws", {})
     key = (device, kind, shape.input, shape.cin, shape.hin, shape.cout)
     ws = cache.get(key)
@@ -228,9 +232,13 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
             # FC2 + threshold + bias sums
             call("rth_heads_backward_branches", ptr(dq), ptr(h1), h1.stride(0), fc2p, Hh, B, A1 - 1, ptr(gh1), g2p,
                  ptr(gb1), ptr(td_abs), ptr(td_acc), st)
-        # FC1
-        gfeat = torch.mm(gh1, w1)
-        gw1 = torch.mm(gh1.t(), feat[:B])
+        # FC1: the two library GEMMs, or (model.FC1_BWD = "hip") both gradients in one rth_fc_bwd call
+        hip = model.fc1_backward(gh1, feat[:B], w1, owner=net)
+        if hip is not None:
+            gfeat, gw1 = hip
+        else:
+            gfeat = torch.mm(gh1, w1)
+            gw1 = torch.mm(gh1.t(), feat[:B])
         if mid is not None:
             mid([gw1, gb1, *g2])
         g = gfeat.view(ys[-1][:B].shape)  # NCHW, like the last conv's output

@@ -1,4 +1,5 @@
-"""Q-networks (PyTorch-ROCm; MIOpen / hipBLASLt run the conv and linear GEMMs in fp32).
+"""Q-networks (PyTorch-ROCm for the plumbing; the conv and FC forwards are hand-written HIP in
+fp32-exact arithmetic, and FC1's backward is hipBLASLt's two GEMMs unless FC1_BWD = "hip").
 
 Parameter names, shapes and the order in which modules are constructed match
 reth/reth/algorithm/dqn/dqn_model.py:6-71, so
@@ -473,6 +474,13 @@ _FC_WS = {}
 # FC1_HEADS -- FC1's split-K reduce and FC2 in one launch (rth_fc1_heads) wherever the heads are
 # computed without autograd: the target pass and the learner's forward (r06); tests patch it
 FC1_HEADS = True
+# FC1_BWD -- FC1's backward (the data gradient gy w and the weight gradient gy^T x): None = the
+# two hipBLASLt GEMMs (torch.mm; the default), "hip" = one rth_fc_bwd call (r07: both gradients
+# on the exact-split bf16 MFMA in one launch, fixed summation order, built like the rest of the
+# library without the packed-FP32 ops) where rth_fc_bwd_supported(B, N, K), else the library
+# GEMMs; in the learner's explicit pass (fused_learner.dueling_grads) and in
+# _LinearReLU.backward; tests patch it
+FC1_BWD = None
 
 
 def _fc_workspace(fn, device, w, M, N, K, owner=None):
@@ -514,23 +522,70 @@ def fc1_relu(x, w, b, out=None, owner=None):
     return torch._addmm_activation(b, x, w.t())
 
 
+def fc1_bwd_workspace(owner, device, B, N, K):
+    """rth_fc_bwd's workspace for (B, N, K): the entry (device, "fc1_bwd", B, N, K) of the owning
+    network's backward workspaces (net._bwd_ws, fused_learner._net_workspace); without an owner a
+    fresh allocation"""
+    from ._lib import lib
+
+    cache = owner.__dict__.setdefault("_bwd_ws", {}) if owner is not None else {}
+    key = (device, "fc1_bwd", B, N, K)
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.empty(max(lib().rth_fc_bwd_workspace(B, N, K), 16) // 4, dtype=torch.float32,
+                                      device=device)
+    return ws
+
+
+def fc1_backward(gy, x, w, want_gx=True, want_gw=True, owner=None):
+    """FC1's backward on rth_fc_bwd: (gx = gy @ w or None, gw = gy.T @ x or None) from the masked
+    output gradient gy [B, N], the input x [B, K] and the weight w [N, K]; None where FC1_BWD is
+    not "hip" or the shape / layout is not built (the caller then runs the library GEMMs).  The
+    workspace is owned by the network that runs it (`owner`: its _bwd_ws, kind "fc1_bwd", keyed by
+    (device, B, N, K) -- two learners never share one and graph replays see a fixed address);
+    without an owner it is allocated per call."""
+    if FC1_BWD != "hip" or not (want_gx or want_gw) or not gy.is_cuda:
+        return None
+    from ._lib import call, lib, ptr, stream_ptr
+
+    (B, N), K = gy.shape, w.shape[1]
+    if not lib().rth_fc_bwd_supported(B, N, K):
+        return None
+    ts = [gy, w.detach()] + ([x] if want_gw else [])
+    if any(t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16 for t in ts) \
+            or not w.is_contiguous():
+        return None
+    ws = fc1_bwd_workspace(owner, gy.device, B, N, K)
+    gx =torch.empty((B, K), dtype=torch.float32, device=gy.device) if want_gx else None
+    gw = torch.empty((N, K), dtype=torch.float32, device=gy.device) if want_gw else None
+    call("rth_fc_bwd", ptr(gy), gy.stride(0), ptr(x) if want_gw else None, x.stride(0) if want_gw else 0,
+         ptr(w) if want_gx else None, B, N, K, ptr(gx), ptr(gw), ptr(ws), stream_ptr())
+    return gx, gw
+
+
 class _LinearReLU(torch.autograd.Function):
     """relu(x @ w.T + b) as one fc1_relu launch (rth_fc_x9, or hipBLASLt's GEMM with a bias+ReLU
     epilogue: torch._addmm_activation has no autograd formula of its own); the backward is the
-    one autograd derives for linear -> relu (threshold on the output, addmm grads)."""
+    one autograd derives for linear -> relu (threshold on the output, addmm grads; the two GEMMs
+    on rth_fc_bwd where FC1_BWD = "hip")."""
 
     @staticmethod
     def forward(ctx, x, w, b, owner=None):
         out = fc1_relu(x, w, b, owner=owner)
         ctx.save_for_backward(x, w, out)
+        ctx.owner = owner
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w, out = ctx.saved_tensors
         g = torch.ops.aten.threshold_backward(g, out, 0)
-        gx = g.mm(w) if ctx.needs_input_grad[0] else None
-        gw = g.t().mm(x) if ctx.needs_input_grad[1] else None
+        hip = fc1_backward(g, x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.owner)
+        if hip is not None:
+            gx, gw = hip
+        else:
+            gx = g.mm(w) if ctx.needs_input_grad[0] else None
+            gw = g.t().mm(x) if ctx.needs_input_grad[1] else None
         gb = g.sum(0) if ctx.needs_input_grad[2] else None
         return gx, gw, gb, None
 
