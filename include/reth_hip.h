@@ -758,6 +758,35 @@ int rth_adam_prenormed(const rth_param_tensor *tensors, int32_t n_tensors, doubl
                        float *total_norm_out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The MLP Q-network (dqn_model.py:59-71, the network of every 1-D observation: CartPole):
+ * Linear(D,H) -> ReLU -> Linear(H,H) -> ReLU -> Linear(H,A) as fused fp32 kernels (mlp.hpp).
+ * `params` (`online`, `target`, `grads`) is a HOST array of six device pointers in torch layout,
+ * read in place: {nn.0.weight [H,D], nn.0.bias [H], nn.2.weight [H,H], nn.2.bias [H],
+ * nn.4.weight [A,H], nn.4.bias [A]}.  Built for H = 128, D in 1..64, A in 1..18, any n, B >= 1;
+ * other shapes return RTH_ERR_INVALID and launch nothing.  Every product is one fp32 fmaf and a
+ * dot product has one fixed summation order, so the Q of a row does not depend on n, on the
+ * row's position or on the entry point; the gradients sum over the batch in a fixed order (no
+ * atomics).  All launches go to `stream`, without host synchronisation or allocation.
+ * ---------------------------------------------------------------------------------- */
+int rth_mlp_supported(int64_t D, int64_t H, int64_t A);            /* 1 where built, else 0 */
+int64_t rth_mlp_workspace(int64_t B, int64_t D, int64_t H, int64_t A); /* bytes for rth_mlp_dqn_grads; < 0: error */
+/* Q[n,A] = net(x[n,D]) (row stride ldx floats); argmax_dev nullable: first index of the row max
+ * (torch.argmax's tie rule, dqn_solver.py:126-131).  One launch. */
+int rth_mlp_q(const float *const *params, const float *x_dev, int64_t ldx, int64_t n, int64_t D, int64_t H, int64_t A,
+              float *q_dev, int32_t *argmax_dev, void *stream);
+/* dqn_solver.py:68-117 for the MLP: Q(s0), Q(s1) online (only if double_q), Q_tgt(s1), the TD /
+ * Huber / IS-weight arithmetic of rth_td_huber (same operation order; isw fp64 cast to f32,
+ * nullable) and the backward through the online net into grads[6] (same order and shapes as
+ * params; every element written, nothing accumulated).  grads == NULL: no backward (calc_loss).
+ * td_abs_dev [B], loss_dev [1] (mean) nullable.  workspace_dev: rth_mlp_workspace(B, D, H, A)
+ * bytes.  At most two launches. */
+int rth_mlp_dqn_grads(const float *const *online, const float *const *target, const float *s0_dev, int64_t lds0,
+                      const float *s1_dev, int64_t lds1, const int64_t *a_dev, const float *r_dev,
+                      const float *done_dev, const double *isw_dev, int64_t B, int64_t D, int64_t H, int64_t A,
+                      float gamma_n, int32_t double_q, float *const *grads, float *td_abs_dev, float *loss_dev,
+                      void *workspace_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Learner -> actor weights: a device-resident latest-wins slot with a device version.
  * Replaces perwez's PUB/SUB CONFLATE weights channel (perwez/perwez/client/socket.py:19-122,
  * 302-328: SendSocket.send / RecvSocket.recv / RecvSocket.empty) as used by

@@ -221,6 +221,13 @@ SIGNATURES = {
     "rth_conv1_relu_wgrad_norm": (c_i32, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f64, c_f64, c_f64, c_vp, c_vp,
                                           ctypes.POINTER(c_i32), c_vp]),
+    # the MLP Q-network (mlp.hpp)
+    "rth_mlp_supported": (c_i32, [c_i64, c_i64, c_i64]),
+    "rth_mlp_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "rth_mlp_q": (c_i32, [ctypes.POINTER(c_vp), c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rth_mlp_dqn_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                  c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_i32, ctypes.POINTER(c_vp), c_vp,
+                                  c_vp, c_vp, c_vp]),
     # learner -> actor weights slot (perwez PUB/SUB CONFLATE)
     "rth_weights_create": (c_i32, [c_i64, c_i32, ctypes.POINTER(c_vp)]),
     "rth_weights_destroy": (c_i32, [c_vp]),

@@ -1,5 +1,6 @@
 """Q-networks (PyTorch-ROCm for the plumbing; the conv and FC forwards are hand-written HIP in
-fp32-exact arithmetic, and FC1's backward is hipBLASLt's two GEMMs unless FC1_BWD = "hip").
+fp32-exact arithmetic, and FC1's backward is hipBLASLt's two GEMMs unless FC1_BWD = "hip"; the
+MLP of 1-D observations is torch.nn.Linear unless MLP_IMPL = "hip": csrc/mlp.hpp's fused kernels).
 
 Parameter names, shapes and the order in which modules are constructed match
 reth/reth/algorithm/dqn/dqn_model.py:6-71, so
@@ -481,6 +482,12 @@ FC1_HEADS = True
 # GEMMs; in the learner's explicit pass (fused_learner.dueling_grads) and in
 # _LinearReLU.backward; tests patch it
 FC1_BWD = None
+# MLP_IMPL -- the MLP Q-network (MLP_DQNNetwork: 1-D observations, CartPole) in DQNSolver: None =
+# torch.nn.Linear forwards, rth_td_huber and torch.autograd (the default), "hip" = the fused fp32
+# kernels of csrc/mlp.hpp (r08: act / act_batch one rth_mlp_q launch, calc_loss and compute_grads
+# one rth_mlp_dqn_grads call of at most two launches) where rth_mlp_supported(D, H, A) on a GPU
+# solver with the default networks, else the torch path; read by DQNSolver at construction
+MLP_IMPL = None
 
 
 def _fc_workspace(fn, device, w, M, N, K, owner=None):
@@ -714,6 +721,42 @@ class MLP_DQNNetwork(nn.Module):
 
     def forward(self, x):
         return self.nn(x)
+
+    # ---------------------------------------------------------------- fused HIP path (MLP_IMPL)
+    def dims(self):
+        """(D, H, A) of the three Linear layers"""
+        return self.nn[0].in_features, self.nn[0].out_features, self.nn[4].out_features
+
+    def _params6(self):
+        """the six parameters in the C ABI's order (rth_mlp_q / rth_mlp_dqn_grads: read in place)"""
+        return [self.nn[0].weight, self.nn[0].bias, self.nn[2].weight, self.nn[2].bias, self.nn[4].weight,
+                self.nn[4].bias]
+
+    def hip_supported(self):
+        """the fused kernels are built for this shape and can read the parameters where they are"""
+        from ._lib import lib
+
+        ps = self._params6()
+        D, H, A = self.dims()
+        return (all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps)
+                and self.nn[2].in_features == H and self.nn[4].in_features == H
+                and lib().rth_mlp_supported(D, H, A) == 1)
+
+    def _mlp_workspace(self, device, B):
+        """rth_mlp_dqn_grads' workspace for B rows, owned by this network and keyed by (device, B)
+        (like fused_learner._net_workspace: two solvers never share one, a replayed graph sees a
+        fixed address)"""
+        from ._lib import lib
+
+        cache = self.__dict__.setdefault("_mlp_ws", {})
+        key = (device, int(B))
+        ws = cache.get(key)
+        if ws is None:
+            size = lib().rth_mlp_workspace(int(B), *self.dims())
+            if size <= 0:
+                raise ValueError(f"rth_mlp_workspace: unsupported shape B={B} (D, H, A)={self.dims()}")
+            ws = cache[key] = torch.empty(size // 4, dtype=torch.float32, device=device)
+        return ws
 
 
 def make_q_network(obs_shape, num_actions, dueling=True):

@@ -7,7 +7,12 @@ rth_conv_bias_relu, FC1 in rth_fc_x9, FC2 in rth_heads_fc2); the dueling Nature-
 update is the explicit kernel sequence of fused_learner.py (HIP data gradients, HIP weight
 gradients of every conv layer, the fused TD / FC2 backward, clip + Adam with the norm from the
 backward; only FC1's two backward GEMMs run on hipBLASLt, unless model.FC1_BWD = "hip"), other
-networks go through torch.autograd.  The TD error,
+networks go through torch.autograd -- except the MLP of 1-D observations (CartPole) under
+model.MLP_IMPL = "hip": act / act_batch are one rth_mlp_q launch (forward + argmax), calc_loss and
+compute_grads one rth_mlp_dqn_grads call (three forwards, TD / Huber, the backward into
+persistent gradient buffers; at most two launches, csrc/mlp.hpp), and clip + Adam follow as
+always; solver.mlp_impl_active says whether that path runs, solver.mlp_hip_launches counts its
+calls.  The TD error,
 double-Q target, Huber loss, IS weighting, mean, |td| and the gradient with respect to Q(s0)
 are ONE HIP kernel (rth_td_huber) wrapped as an autograd Function on the autograd path, so
   * the loss' backward starts from the kernel's d(loss)/d(Q(s0)) -- no chain of small torch
@@ -21,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, fused_learner
+from . import model as _model
 from ._lib import call, ptr, stream_ptr
 from .model import default_models
 from .optim import ClipAdam
@@ -183,6 +189,16 @@ class DQNSolver(Algorithm):
         # torch.autograd over the same forward (the A/B reference)
         self.fused_grads = True
         self.td_mean_acc = None  # Trainer's device mean-|td| accumulator (fused pass adds to it)
+        # the MLP on the fused HIP kernels (model.MLP_IMPL, read here): active only for two
+        # MLP_DQNNetwork on the GPU in a shape rth_mlp_supported builds; else the torch path
+        self.mlp_impl = _model.MLP_IMPL
+        self.mlp_hip_launches = 0  # HIP calls of that path (tests: no silent fallback)
+        self.mlp_impl_active = "hip" if self.mlp_impl == "hip" and self._mlp_eligible() else None
+        if self.mlp_impl_active == "hip":
+            # persistent gradient buffers (fixed addresses: a captured update replays) and the
+            # ABI's pointer arrays of the parameters, which are read and updated in place
+            self._mlp_grads = [torch.empty_like(p) for p in self.q_network._params6()]
+            self._mlp_arrays()
 
     # ------------------------------------------------------------------ target / weights
     @torch.no_grad()
@@ -245,9 +261,67 @@ class DQNSolver(Algorithm):
                 q1o = self.q_network(s1) if self.double_q else None
         return q1o, q1t
 
+    # ------------------------------------------------------------------ MLP on HIP (mlp.hpp)
+    def _mlp_eligible(self):
+        q, t = self.q_network, self.target_q_network
+        return (type(q) is _model.MLP_DQNNetwork and type(t) is _model.MLP_DQNNetwork and q.dims() == t.dims()
+                and q.hip_supported() and t.hip_supported())
+
+    def _mlp_arrays(self):
+        """the host pointer arrays (online, target, grads) of the ABI, rebuilt when a parameter's
+        storage moved (load_state_dict(assign=True), .to())"""
+        key = tuple(p.data_ptr() for p in self.q_network._params6() + self.target_q_network._params6())
+        if getattr(self, "_mlp_key", None) != key:
+            mk = lambda ts: (_lib.c_vp * 6)(*[t.data_ptr() for t in ts])
+            self._mlp_ptrs = (mk(self.q_network._params6()), mk(self.target_q_network._params6()),
+                              mk(self._mlp_grads))
+            self._mlp_key = key
+        return self._mlp_ptrs
+
+    def _mlp_states(self, x):
+        """observations as a float32 device matrix [n, D] with unit column stride"""
+        D = self.q_network.dims()[0]
+        x = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(self.device, torch.float32)
+        x = x.reshape(-1, D)
+        return x if x.stride(1) == 1 and x.stride(0) >= D else x.contiguous()
+
+    def _mlp_q(self, x):
+        """(Q [n, A], argmax [n] int32) of the online network: one rth_mlp_q launch"""
+        D, H, A = self.q_network.dims()
+        n = x.shape[0]
+        q = torch.empty((n, A), dtype=torch.float32, device=self.device)
+        am = torch.empty(n, dtype=torch.int32, device=self.device)
+        call("rth_mlp_q", self._mlp_arrays()[0], ptr(x), x.stride(0), n, D, H, A, ptr(q), ptr(am), stream_ptr())
+        self.mlp_hip_launches += 1
+        return q, am
+
+    def _mlp_td(self, s0, a, r, s1, done, isw, backward):
+        """one rth_mlp_dqn_grads call -> (loss [1], |td| [B]); backward: the gradients land in
+        the persistent buffers"""
+        D, H, A = self.q_network.dims()
+        s0, s1 = self._mlp_states(s0), self._mlp_states(s1)
+        B = s0.shape[0]
+        a, r, done = a.contiguous().view(-1), r.contiguous().view(-1), done.contiguous().view(-1)
+        if isw is not None:
+            isw = isw.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
+        if s1.shape[0] != B or a.numel() != B or r.numel() != B or done.numel() != B or (
+                isw is not None and isw.numel() != B):
+            raise ValueError("batch columns disagree in length")
+        online, target, grads = self._mlp_arrays()
+        td_abs = torch.empty(B, dtype=torch.float32, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        ws = self.q_network._mlp_workspace(self.device, B)
+        call("rth_mlp_dqn_grads", online, target, ptr(s0), s0.stride(0), ptr(s1), s1.stride(0), ptr(a), ptr(r),
+             ptr(done), ptr(isw), B, D, H, A, self.gamma_n, int(bool(self.double_q)), grads if backward else None,
+             ptr(td_abs), ptr(loss), ptr(ws), stream_ptr())
+        self.mlp_hip_launches += 1
+        return loss, td_abs
+
     def calc_loss_device(self, batch):
         """|td| on the device without an update (:100-102)"""
         s0, a, r, s1, done = self._tensors(batch)
+        if self.mlp_impl_active == "hip":
+            return self._mlp_td(s0, a, r, s1, done, None, backward=False)[1]
         with torch.no_grad():
             q0 = self.q_network.forward_heads(s0) if self._heads else self.q_network(s0)
         q1o, q1t = self._forward_targets(s1)
@@ -268,6 +342,12 @@ class DQNSolver(Algorithm):
         step count itself (fused_learner.NORM_IN_BACKWARD)"""
         s0, a, r, s1, done = self._tensors(batch)
         isw = None if weights is None else (weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights)))
+        if self.mlp_impl_active == "hip" and q1t is None:  # (a precomputed q1t: the torch path below)
+            loss, td_abs = self._mlp_td(s0, a, r, s1, done, isw, backward=True)
+            for p, g in zip(self.q_network._params6(), self._mlp_grads):
+                p.grad = g
+            self.last_loss = loss.view(())
+            return td_abs  # (not mean-tracked: Trainer adds mean |td| itself)
         if self.fused_grads and self._heads and fused_learner.eligible(self.q_network, s0, s1):
             loss, td_abs = fused_learner.dueling_grads(self, s0, a, r, s1, done, isw, q1t, td_acc=self.td_mean_acc,
                                                         mid=mid, probe=probe, prenorm=prenorm)
@@ -327,9 +407,20 @@ class DQNSolver(Algorithm):
     # ------------------------------------------------------------------ acting
     @torch.no_grad()
     def act(self, state):
+        if self.mlp_impl_active == "hip":  # forward + argmax in one launch
+            return int(self._mlp_q(self._mlp_states(state))[1].item())
         x = torch.as_tensor(np.asarray(state), dtype=torch.float32).to(self.device).unsqueeze(0) \
             if not torch.is_tensor(state) else state.to(self.device, torch.float32).unsqueeze(0)
         return int(torch.argmax(self.q_network(x), dim=1).item())
+
+    @torch.no_grad()
+    def act_batch(self, states):
+        """greedy actions of n states as an int32 device tensor [n], no host synchronisation (the
+        MLP on HIP: the same single launch as act)"""
+        if self.mlp_impl_active == "hip":
+            return self._mlp_q(self._mlp_states(states))[1]
+        x = (states if torch.is_tensor(states) else torch.as_tensor(np.asarray(states))).to(self.device, torch.float32)
+        return torch.argmax(self.q_network(x), dim=1).to(torch.int32)
 
 
 def get_solver(name, **kwargs):
