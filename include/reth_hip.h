@@ -787,6 +787,54 @@ int rth_mlp_dqn_grads(const float *const *online, const float *const *target, co
                       void *workspace_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Device-resident vectorised CartPole actors on the MLP kernels (csrc/mlp_actor.hpp): N gym
+ * CartPole-v0/v1 environments stepped by one launch, without host synchronisation.  Replaces the
+ * host actor loop of reth/reth/presets/worker.py:128-155 (Worker.step: act, env.step, env.reset on
+ * done) and what it calls: utils/exploration.py:26-31 (RandomExploration.act),
+ * algorithm/dqn/dqn_solver.py:126-131 (act = argmax Q) and utils/nstep_adder.py:11-28.
+ * All pointers are device memory except `params` (a host array of six device pointers, as
+ * rth_mlp_q's).  Built for D = 4, H = 128, A = 2.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rth_mlp_actor_args {
+  const float *const *params; /* the acting network (rth_mlp_q layout); unused by the reset */
+  int64_t D, H, A;
+  double *state;              /* [N, 4] fp64 env state (x, x_dot, theta, theta_dot) */
+  int32_t *ep_steps;          /* [N] steps taken in the running episode */
+  int64_t *t_dev;             /* [N] env steps taken, one (equal) copy per env: the Philox counter */
+  int64_t *stats;             /* [N, 3] finished episodes, sum of their lengths, last length */
+  float *obs_ring;            /* [N * ring + 1, 4] f32 observations, 16-byte aligned; last row: zero sink */
+  int64_t *cur_slot;          /* [N] ring slot of the observation acted on next */
+  const double *eps;          /* [N] exploration rates, read every step */
+  const int64_t *action_in;   /* [N] nullable: overrides the ε-greedy choice (tests) */
+  int64_t *action;            /* out [N]: this step's transition ... */
+  float *reward, *done;       /* out [N] */
+  int64_t *s0_h, *s1_h;       /* out [N]: observation handles env * ring + slot */
+  int32_t *emit;              /* out [N]: 1 where the adder emitted a row; its fields: */
+  int64_t *row_s0, *row_a, *row_s1;
+  float *row_r, *row_done;
+  float *row_obs0, *row_obs1; /* out [N, 4]: the emitted row's observations by value (16-byte aligned) */
+  float *q_out;               /* out [N, A] nullable: the acting Q rows (equal to rth_mlp_q's) */
+  uint64_t seed;              /* exploration and reset seed */
+  int64_t N;
+  int32_t ring;               /* slots per env: >= 4 and >= 2 (n_step + 2) */
+  int32_t max_episode_steps;  /* TimeLimit: 200 (v0) / 500 (v1) */
+} rth_mlp_actor_args;
+/* env.reset() of every env (worker.py:144-145): states from Philox(seed, env, t = 0) -- the counter
+ * layout is documented in csrc/mlp_actor.hpp --, ep_steps / t_dev / stats = 0, the observation into
+ * ring slot 1, cur_slot = 1.  Uses state, ep_steps, t_dev, stats, obs_ring, cur_slot, seed, N, ring.
+ * Arguments are checked before anything is launched (RTH_ERR_INVALID, rth_last_error). */
+int rth_cartpole_reset(const rth_mlp_actor_args *args, void *stream);
+/* One env step of all N actors (Worker.step, worker.py:128-155), one launch: Q of the current observations
+ * (rth_mlp_q's values), ε-greedy with rth_eps_greedy's draws at counter t = t_dev + 1
+ * (exploration.py:26-31, dqn_solver.py:126-131), CartPole dynamics in fp64, reward 1, done on
+ * |x| > 2.4, |theta| > 12 degrees or ep_steps reaching max_episode_steps; a finished episode's env
+ * is reset (Philox(seed, env, t)); next observation to ring slot (2t) % ring, reset observation
+ * to (2t + 1) % ring; the transition is pushed into the adder `h` (nstep_adder.py:11-28, as
+ * rth_nstep_push) and an emitted row is written as handles and by value.  args->N must equal the
+ * adder's.  Arguments are checked before anything is launched. */
+int rth_mlp_actor_step(rth_nstep *h, const rth_mlp_actor_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Learner -> actor weights: a device-resident latest-wins slot with a device version.
  * Replaces perwez's PUB/SUB CONFLATE weights channel (perwez/perwez/client/socket.py:19-122,
  * 302-328: SendSocket.send / RecvSocket.recv / RecvSocket.empty) as used by

@@ -4,28 +4,13 @@
 // Reference: reth/reth/utils/exploration.py:26-31 (RandomExploration.act),
 // reth/reth/algorithm/dqn/dqn_solver.py:126-131 (act = argmax Q),
 // reth/reth/utils/nstep_adder.py:5-28 (NStepAdder), test/apex-dqn/worker.py:21-61.
+#include "actor_shared.hpp"
 #include "common.hpp"
 
 namespace rth {
 
 // ------------------------------------------------------------------ epsilon-greedy
-// One lane per actor: A <= 18 for Atari, so the row argmax is a short in-register loop and
-// the launch is one wave per 64 actors.
-__device__ inline int64_t eps_greedy_one(const float *__restrict__ q, int64_t i, int A, int dueling,
-                                         const double *__restrict__ eps, const double *__restrict__ u_in,
-                                         const int64_t *__restrict__ ra_in, uint64_t seed, uint64_t counter) {
-  const double u = u_in ? u_in[i] : philox_uniform(seed, counter, (uint32_t)i, STREAM_EXPLORE);
-  if (u < eps[i]) {
-    if (ra_in) return ra_in[i];
-    uint32_t c[4] = {(uint32_t)i, (uint32_t)counter, (uint32_t)(counter >> 32), STREAM_RANDACT};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    return (int64_t)(((uint64_t)c[0] * (uint64_t)A) >> 32);  // uniform in [0, A)
-  }
-  float qr[kMaxActions];
-  q_row(q + i * (A + dueling), A, dueling, qr);
-  return argmax_first(qr, A);
-}
-
+// (eps_greedy_one: actor_shared.hpp)
 __global__ void k_eps_greedy(const float *__restrict__ q, int64_t N, int A, int dueling, const double *__restrict__ eps,
                              const double *__restrict__ u_in, const int64_t *__restrict__ ra_in, uint64_t seed,
                              uint64_t counter, const int64_t *__restrict__ counter_dev, int64_t *__restrict__ out) {
@@ -36,59 +21,7 @@ __global__ void k_eps_greedy(const float *__restrict__ q, int64_t N, int A, int 
 }
 
 // ------------------------------------------------------------------ n-step adder
-// Per actor: a deque of up to n pending rows, position 0 = newest (appendleft), SoA in HBM.
-struct NStepState {
-  int32_t *count;
-  int64_t *s0, *a, *s1;
-  float *r, *done;
-};
-
-__device__ inline void nstep_push_one(const NStepState &st, int64_t i, int n, double gamma, int mode, int64_t s0,
-                                      int64_t a, float rn, int64_t s1n, float done, int32_t *__restrict__ emit,
-                                      int64_t *__restrict__ s0_out, int64_t *__restrict__ a_out,
-                                      float *__restrict__ r_out, int64_t *__restrict__ s1_out,
-                                      float *__restrict__ done_out) {
-  const int64_t base = i * n;
-  int count = st.count[i];
-  int emitted = 0;
-  if (count == n) {  // deque full: pop the oldest (nstep_adder.py:13-14)
-    const int64_t k = base + count - 1;
-    s0_out[i] = st.s0[k];
-    a_out[i] = st.a[k];
-    r_out[i] = st.r[k];
-    s1_out[i] = st.s1[k];
-    done_out[i] = st.done[k];
-    --count;
-    emitted = 1;
-  }
-  emit[i] = emitted;
-  double t_gamma = gamma;
-  for (int k = 0; k < count; ++k) {  // newest -> oldest (nstep_adder.py:16-25)
-    const int64_t p = base + k;
-    if (st.done[p] != 0.0f) break;
-    if (mode == 0)  // numpy 1.19: f64 product, += casts back to the f32 row
-      st.r[p] = (float)radd((double)st.r[p], rmul(t_gamma, (double)rn));
-    else            // numpy 2 / NEP 50: the python float is weak, product stays f32
-      st.r[p] = radd(st.r[p], rmul((float)t_gamma, rn));
-    t_gamma = rmul(t_gamma, gamma);
-    st.s1[p] = s1n;
-  }
-  for (int k = count; k > 0; --k) {  // appendleft
-    const int64_t p = base + k;
-    st.s0[p] = st.s0[p - 1];
-    st.a[p] = st.a[p - 1];
-    st.r[p] = st.r[p - 1];
-    st.s1[p] = st.s1[p - 1];
-    st.done[p] = st.done[p - 1];
-  }
-  st.s0[base] = s0;
-  st.a[base] = a;
-  st.r[base] = rn;
-  st.s1[base] = s1n;
-  st.done[base] = done;
-  st.count[i] = count + 1;
-}
-
+// (NStepState, nstep_push_one and the rth_nstep handle: actor_shared.hpp)
 __global__ void k_nstep_push(NStepState st, int64_t N, int n, double gamma, int mode,
                              const int64_t *__restrict__ s0, const int64_t *__restrict__ a,
                              const float *__restrict__ r, const int64_t *__restrict__ s1,
@@ -296,16 +229,6 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact_flagged(const float
 }  // namespace rth
 
 using namespace rth;
-
-struct rth_nstep {
-  int64_t N;
-  int32_t n;
-  double gamma;
-  int32_t mode;
-  int device;
-  void *mem;
-  NStepState st;
-};
 
 // the actor step's first launch: the step counter (what ε-greedy and the env step read) and
 // the acting stacks' frame-ring rows, rows[i] = i * ring + cur_slot[i] (was two launches)

@@ -1,0 +1,175 @@
+"""Vectorised CartPole actors on one GPU, on the fused MLP kernels (csrc/mlp_actor.hpp).
+
+Reference actor loop: reth/reth/presets/worker.py:128-155 (Worker.step: exploration.act ->
+solver.act, env.step, env.reset on done) and utils/nstep_adder.py:11-28, one host env and one
+transition at a time.  Here N gym CartPole-v0/v1 environments (the dynamics of envs.CartPole, fp64) live in HBM
+and step together in ONE launch per env step (rth_mlp_actor_step): the acting forward of the MLP
+Q-network (bit-equal to rth_mlp_q), ε-greedy with rth_eps_greedy's Philox draws, the dynamics,
+the reset of finished episodes, the f32 observations into a per-env ring and the n-step push.
+Emitted n-step rows come out as ring handles and by value (row_obs0 / row_obs1 [N, 4]), so
+DQNSolver.calc_loss_device and HbmReplay.append consume them as dense tensors.  No host
+synchronisation anywhere; every per-step scalar is device-resident, so a captured step replays.
+
+The counterpart of actors.VecActors (conv observations) for 1-D observations.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_ptr
+from .actors import apex_epsilons
+
+OBS_DIM, NUM_ACTIONS = 4, 2
+
+
+class VecCartPoleActors:
+    def __init__(self, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=200, nstep_mode=0,
+                 device=None):
+        self.N = int(n_actors)
+        self.n_step, self.gamma = int(n_step), float(gamma)
+        self.gamma_n = float(np.float32(gamma ** n_step))
+        self.seed = int(seed)
+        self.max_episode_steps = int(max_episode_steps)
+        if self.N < 1 or self.n_step < 1 or self.max_episode_steps < 1:
+            raise ValueError("n_actors, n_step and max_episode_steps must be >= 1")
+        self.device = torch.device(device if device is not None else "cuda")
+        ring = 4
+        while ring < 2 * (self.n_step + 3):  # an emitted row's observations are at most n + 1 steps old, 2 slots a step
+            ring *= 2
+        self.ring = ring
+        N = self.N
+        z = self._alloc
+        self.state = z((N, 4), torch.float64)
+        self.ep_steps = z((N,), torch.int32)
+        self.t_dev = z((N,), torch.int64)          # env steps taken, one equal copy per env (the Philox counter)
+        self.stats = z((N, 3), torch.int64)        # finished episodes, sum of their lengths, last length
+        self.obs_ring = z((N * ring + 1, OBS_DIM), torch.float32)  # zero-filled once; last row: the sink
+        self.cur_slot = z((N,), torch.int64)
+        e = apex_epsilons(N) if eps is None else np.array(np.broadcast_to(np.asarray(eps, np.float64), (N,)))
+        # float64, read by every step: overwrite in place (eps.copy_ / eps.fill_) to follow a schedule
+        self.eps = z((N,), torch.float64)
+        self.eps.copy_(torch.as_tensor(e, dtype=torch.float64))
+        self.action, self.s0_h, self.s1_h = z((N,), torch.int64), z((N,), torch.int64), z((N,), torch.int64)
+        self.reward, self.done = z((N,), torch.float32), z((N,), torch.float32)
+        self.emit = z((N,), torch.int32)
+        self.row_s0, self.row_a, self.row_s1 = z((N,), torch.int64), z((N,), torch.int64), z((N,), torch.int64)
+        self.row_r, self.row_done = z((N,), torch.float32), z((N,), torch.float32)
+        self.row_obs0, self.row_obs1 = z((N, OBS_DIM), torch.float32), z((N, OBS_DIM), torch.float32)
+        self.q_out = None  # want_q(): the acting Q rows [N, A] (tests)
+        self._base = torch.arange(N, device=self.device, dtype=torch.int64) * ring
+        h = _lib.c_vp()
+        with torch.cuda.device(self.device):
+            call("rth_nstep_create", N, self.n_step, self.gamma, int(nstep_mode), torch.cuda.current_device(),
+                 _lib.ctypes.byref(h))
+        self._nstep = h.value
+        self._params_key = self._params_arr = None
+        self.pushes = 0    # env steps issued (host mirror of t_dev)
+        self.launches = 0  # rth_mlp_actor_step calls: one launch each
+        self.reset()
+
+    def _alloc(self, shape, dtype):
+        """a zero-filled device buffer (tests override it to surround every buffer with guards)"""
+        return torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def __del__(self):
+        if getattr(self, "_nstep", None):
+            try:
+                _lib.lib().rth_nstep_destroy(self._nstep)
+            except Exception:
+                pass
+            self._nstep = None
+
+    # ------------------------------------------------------------------ ABI arguments
+    def _params(self, q_network):
+        ps = q_network._params6()
+        key = tuple(p.data_ptr() for p in ps)
+        if key != self._params_key:
+            if not q_network.hip_supported() or q_network.dims() != (OBS_DIM, 128, NUM_ACTIONS):
+                raise ValueError(f"the CartPole actors run MLP_DQNNetwork((4,), 2) on the GPU, got dims {q_network.dims()}")
+            self._params_arr = (_lib.c_vp * 6)(*key)
+            self._params_key = key
+        return self._params_arr
+
+    def _args(self, params=None, action_in=None):
+        return _lib.MlpActorArgs(params, OBS_DIM, 128, NUM_ACTIONS, ptr(self.state), ptr(self.ep_steps),
+                                 ptr(self.t_dev), ptr(self.stats), ptr(self.obs_ring), ptr(self.cur_slot),
+                                 ptr(self.eps), ptr(action_in), ptr(self.action), ptr(self.reward), ptr(self.done),
+                                 ptr(self.s0_h), ptr(self.s1_h), ptr(self.emit), ptr(self.row_s0), ptr(self.row_a),
+                                 ptr(self.row_s1), ptr(self.row_r), ptr(self.row_done), ptr(self.row_obs0),
+                                 ptr(self.row_obs1), ptr(self.q_out), self.seed, self.N, self.ring,
+                                 self.max_episode_steps)
+
+    # ------------------------------------------------------------------ env
+    def reset(self):
+        """env.reset() of every env (states from Philox(seed, env, t = 0)), an empty adder, zeroed
+        step counters and episode statistics"""
+        s = stream_ptr()
+        args = self._args()
+        call("rth_cartpole_reset", _lib.ctypes.byref(args), s)
+        call("rth_nstep_reset", self._nstep, s)
+        self.pushes = 0
+
+    def want_q(self, on=True):
+        """have every step also write its acting Q rows to q_out [N, A] (tests)"""
+        self.q_out = self._alloc((self.N, NUM_ACTIONS), torch.float32) if on else None
+        return self.q_out
+
+    @torch.no_grad()
+    def set_state(self, states, steps=None):
+        """inject env states [N, 4] (float64) and, optionally, the running episodes' step counts
+        [N]; the observations the envs act on next become float32(states) (tests)"""
+        st = torch.as_tensor(np.asarray(states, np.float64) if not torch.is_tensor(states) else states)
+        self.state.copy_(st.to(self.device, torch.float64).reshape(self.N, 4))
+        if steps is not None:
+            sp = torch.as_tensor(np.asarray(steps) if not torch.is_tensor(steps) else steps)
+            self.ep_steps.copy_(sp.to(self.device, torch.int32).reshape(self.N))
+        self.obs_ring[self._base + self.cur_slot] = self.state.to(torch.float32)
+
+    def current_obs(self):
+        """the observations [N, 4] the envs act on next (a copy)"""
+        return self.obs_ring[self._base + self.cur_slot]
+
+    @property
+    def warm(self):
+        """every actor emits one n-step row per step once its deque is full"""
+        return self.pushes > self.n_step
+
+    @torch.no_grad()
+    def step(self, q_network, action_in=None):
+        """one env step for every actor, one launch; action_in (int64 [N], device) overrides the
+        ε-greedy choice.  Returns True when rows were emitted (warm)."""
+        if action_in is not None:
+            if not (torch.is_tensor(action_in) and action_in.is_cuda and action_in.dtype == torch.int64
+                    and action_in.numel() == self.N and action_in.is_contiguous()):
+                raise ValueError("action_in: a contiguous int64 device tensor [N]")
+        args = self._args(self._params(q_network), action_in)
+        call("rth_mlp_actor_step", self._nstep, _lib.ctypes.byref(args), stream_ptr())
+        self.launches += 1
+        self.pushes += 1
+        return self.warm
+
+    # ------------------------------------------------------------------ rows
+    def rows(self):
+        """the emitted n-step rows [s0, a, r, s1, done] as the live dense device tensors the next
+        step overwrites (valid once warm): what calc_loss_device / append consume"""
+        return [self.row_obs0, self.row_a, self.row_r, self.row_obs1, self.row_done]
+
+    def append(self, replay, td_abs):
+        """Client.append of the emitted rows (every actor emits once warm)"""
+        if not self.warm:
+            raise RuntimeError("no rows yet: the adders fill during the first n_step steps")
+        return replay.append(self.rows(), td_abs)
+
+    def episode_stats(self):
+        """per-env device statistics (int64 [N] each): finished episodes, the sum of their lengths,
+        the last finished length"""
+        return self.stats[:, 0], self.stats[:, 1], self.stats[:, 2]
+
+    @staticmethod
+    def columns():
+        """replay columns of the rows [s0, a, r, s1, done], cast f4 / i8 / f4 / f4 / f4 as
+        test/apex-dqn/worker.py:47-51 casts them"""
+        from .replay import Column
+
+        return [Column((OBS_DIM,), torch.float32), Column((), torch.int64), Column((), torch.float32),
+                Column((OBS_DIM,), torch.float32), Column((), torch.float32)]

@@ -1,0 +1,186 @@
+"""Ape-X DQN for 1-D observations on one GPU and one stream: the device CartPole loop.
+
+The counterpart of apex.ApexDQN (conv observations) on the fused MLP kernels.  Reference wiring:
+reth/examples/dqn/run.py (worker.step_batch -> solver.calc_loss -> buffer.append_batch ->
+buffer.sample -> trainer.step -> buffer.update_priorities) with the actor side of
+presets/worker.py:128-155.  One iteration, entirely in HBM and without host synchronisation:
+
+    1. VecCartPoleActors.step           one launch: act, env, reset, n-step push (N env steps)
+    2. solver.calc_loss_device(rows)    the emitted rows' |td|: their priorities
+    3. HbmReplay.append                 PER insert of the N rows
+    4. once sample_start rows are stored:
+       sample_into (preallocated batch) -> solver.update_device(batch, isw) ->
+       update_priorities(idx, |td|, step=True)
+
+Which of the steps run is decided on the host from counts it already knows (every actor emits
+one row per step once warm): nothing is read back.  The target sync runs on the host Interval
+outside the iteration, as ApexDQN does it.  capture() records the steady-state iteration as one
+HIP graph; every per-step scalar (env step counters, FIFO tail, Philox counters, the schedules,
+Adam's step count) is device-resident, so the graph replays.
+
+The loop needs the MLP's fused kernels (model.MLP_IMPL = "hip"): without them it refuses to
+construct -- there is no torch fallback here.
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import model
+from .mlp_actors import NUM_ACTIONS, OBS_DIM, VecCartPoleActors
+from .replay import HbmReplay
+from .schedule import Interval
+from .solver import Box, DQNSolver, Discrete
+
+
+@dataclass
+class MlpApexConfig:
+    n_actors: int = 64
+    batch_size: int = 64
+    capacity: int = 100_000
+    n_step: int = 1
+    gamma: float = 0.99
+    alpha: float = 0.6                 # reth/examples/dqn/config.yaml
+    beta: str = "0.4,1,100000"
+    learning_rate: float = 1e-3
+    adam_epsilon: float = 1e-8
+    clip_value: float = 40.0
+    double_q: bool = True
+    update_target_interval: int = 200
+    sample_start: int = 1000           # rows stored before the first update
+    max_episode_steps: int = 200       # CartPole-v0 (500: v1)
+    nstep_mode: int = 0
+    eps: Optional[object] = None       # None: apex_epsilons(n_actors)
+    seed: int = 0
+
+
+class MlpApexDQN:
+    def __init__(self, cfg: MlpApexConfig = None, device=None):
+        cfg = cfg if cfg is not None else MlpApexConfig()
+        if model.MLP_IMPL != "hip":
+            raise RuntimeError('MlpApexDQN runs on the fused MLP kernels: set reth_amd.model.MLP_IMPL = "hip" before '
+                               f"constructing it (MLP_IMPL is {model.MLP_IMPL!r}); there is no torch fallback")
+        if cfg.sample_start < 1 or cfg.batch_size < 1:
+            raise ValueError("sample_start and batch_size must be >= 1")
+        self.cfg = cfg
+        self.device = torch.device(device if device is not None else "cuda")
+        torch.manual_seed(cfg.seed)
+        self.solver = DQNSolver(Box(-1, 1, (OBS_DIM,)), Discrete(NUM_ACTIONS), gamma=cfg.gamma,
+                                clip_value=cfg.clip_value, double_q=cfg.double_q, dueling=True,
+                                learning_rate=cfg.learning_rate, adam_epsilon=cfg.adam_epsilon,
+                                update_target_interval=cfg.update_target_interval, device=self.device,
+                                n_step=cfg.n_step)
+        if self.solver.mlp_impl_active != "hip":
+            raise RuntimeError("the MLP's HIP kernels are not active for this solver (rth_mlp_supported)")
+        # the target sync: host Interval outside the (possibly captured) iteration
+        self.solver.auto_target_update = False
+        self._target_interval = Interval(self.solver.update_target, cfg.update_target_interval)
+        self.actors = VecCartPoleActors(cfg.n_actors, cfg.n_step, cfg.gamma, eps=cfg.eps, seed=cfg.seed,
+                                        max_episode_steps=cfg.max_episode_steps, nstep_mode=cfg.nstep_mode,
+                                        device=self.device)
+        self.replay = HbmReplay(cfg.capacity, VecCartPoleActors.columns(), cfg.alpha, cfg.beta, self.device,
+                                seed=cfg.seed + 7919)
+        self.batch, self.idx, self.isw = self.replay.new_batch(cfg.batch_size)
+        self.iterations = 0
+        self.env_steps = 0
+        self.rows_emitted = 0  # = rows appended: every emitted row is stored
+        self.updates = 0
+        self.solver_calls = 0  # calc_loss_device + update_device calls issued (solver.mlp_hip_launches)
+        self._graph = None
+        self._graph_keep = None
+
+    # ------------------------------------------------------------------ one iteration
+    def _learning(self):
+        """the update runs in this iteration: sample_start rows are stored (host counts only)"""
+        return min(self.rows_emitted, self.cfg.capacity) >= self.cfg.sample_start
+
+    def _body(self, learn):
+        """the device work of one iteration with warm actors; returns the update's |td| or None"""
+        act = self.actors
+        act.step(self.solver.q_network)
+        td = self.solver.calc_loss_device(act.rows())
+        act.append(self.replay, td)
+        if not learn:
+            return None
+        self.replay.sample_into(self.cfg.batch_size, self.batch, self.idx, self.isw)
+        td_b = self.solver.update_device(self.batch, self.isw)
+        self.replay.update_priorities(self.idx, td_b, step=True)
+        return td_b
+
+    def iteration(self):
+        """one iteration on the current stream; never synchronises with the host"""
+        act, N = self.actors, self.actors.N
+        if self._graph is not None:
+            self._graph.replay()
+            act.pushes += 1
+            act.launches += 1
+            self.rows_emitted += N
+            # host mirrors of what the replayed launches advanced on the device
+            self.solver.mlp_hip_launches += 2
+            self.solver_calls += 2
+            self.replay.alpha.step()
+            self.replay.beta.step()
+            learned = True
+        elif act.pushes < act.n_step:  # the adders fill: this step emits no rows yet
+            act.step(self.solver.q_network)
+            learned = False
+        else:
+            self.rows_emitted += N  # this step emits N rows
+            learned = self._learning()
+            self._body(learned)
+            self.solver_calls += 2 if learned else 1
+        self.iterations += 1
+        self.env_steps += N
+        if learned:
+            self.updates += 1
+            self._target_interval()
+
+    def run(self, iterations):
+        for _ in range(int(iterations)):
+            self.iteration()
+
+    # ------------------------------------------------------------------ graph
+    def graph_ready(self):
+        """the next iteration is the steady-state one: rows flow and the update runs"""
+        return self.actors.pushes >= self.actors.n_step and \
+            min(self.rows_emitted + self.actors.N, self.cfg.capacity) >= self.cfg.sample_start and self.updates >= 1
+
+    def capture(self):
+        """record the steady-state iteration (actor step, priorities, append, sample, update,
+        priority update) as one HIP graph on a side stream; iteration() replays it from then
+        on.  Capturing records and does not run the iteration.  After a capture the C library's
+        host mirrors of the replay counters (HbmReplay.info) no longer advance -- the device
+        state does; rows_emitted / updates here are the counts."""
+        if self._graph is not None:
+            return
+        if not self.graph_ready():
+            raise RuntimeError("capture() records the steady-state iteration: run iteration() until at least one "
+                               "update has run (graph_ready())")
+        act, solver, rep = self.actors, self.solver, self.replay
+        host = (act.pushes, act.launches, solver.mlp_hip_launches, rep.alpha.cur_step, rep.beta.cur_step)
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+            keep = self._body(True)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        act.pushes, act.launches, solver.mlp_hip_launches, rep.alpha.cur_step, rep.beta.cur_step = host
+        self._graph, self._graph_keep = g, keep
+
+    # ------------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def greedy_eval(self, n_envs=256, seed=12345, max_steps=None):
+        """mean length of the first episode of each of n_envs greedy (ε = 0) envs of a separate
+        actor set under the current online network, from the device statistics.  Every env finishes
+        its first episode within max_episode_steps steps (TimeLimit); taking each env's first
+        episode -- not every episode finished in the window -- keeps short episodes from counting
+        more often than long ones.  One host read, at the end."""
+        ev = VecCartPoleActors(n_envs, 1, self.cfg.gamma, eps=0.0, seed=seed,
+                               max_episode_steps=self.cfg.max_episode_steps, device=self.device)
+        first = torch.zeros(ev.N, dtype=torch.int64, device=self.device)
+        episodes, _, last = ev.episode_stats()
+        for _ in range(self.cfg.max_episode_steps if max_steps is None else int(max_steps)):
+            ev.step(self.solver.q_network)
+            first = torch.where((first == 0) & (episodes > 0), last, first)
+        done = first > 0
+        return float((first.sum() / done.sum().clamp(min=1)).item())
