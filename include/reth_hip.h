@@ -355,6 +355,45 @@ int rth_actor_tail(rth_nstep *h, const rth_actor_tail_args *args, int32_t *emit_
 /* initial reset of every actor into slot 1 (t = 0) */
 int rth_synth_env_reset(uint8_t *frames_dev, int64_t n_actors, int32_t ring, uint64_t seed,
                         int64_t *cur_slot_dev, void *stream);
+/* "Paddle": a device-resident pixel game as the env of the same frame ring (csrc/game.hpp: the
+ * exact integer rules, the Philox draws on stream 8 and the render; reth_amd.envs.Paddle restates
+ * them on the host bit for bit).  One instance per actor; reward and episode end follow from the
+ * action.  It honours the host loop's contract -- reth/reth/presets/worker.py:128-155 (Worker.step:
+ * env.step, env.reset() on done, the terminal observation kept as the done row's s1) and
+ * reth/reth/env/util.py:179-209 (FrameStack: reset = the first frame x4, step = shift in the new
+ * frame) -- with rth_synth_env_step's slot arithmetic: step t writes the next stack into slot
+ * (2t) % ring and, on done, the reset stack into (2t + 1) % ring; cur_slot and the s0 / s1 handles
+ * are written the same way, so the heads cache, rth_compact_flagged and rth_replay_push_frames work
+ * unchanged.  The game's tensors are the caller's; env i's state and stats rows are written by its
+ * own workgroup only (no atomics, nothing zero-filled per step). */
+typedef struct rth_game_args {
+  int32_t *state;            /* [N, 8] ball_x, ball_y, vx, vy, paddle_x, balls_left, ep_return, ep_steps;
+                              * 16-byte aligned */
+  int64_t *stats;            /* [N, 4] episodes finished, sum of their returns, last return, last length */
+  const int64_t *action_in;  /* [N] nullable, rth_game_actor_tail only: overrides the ε-greedy choice */
+  uint64_t seed;             /* spawn / reset draws */
+  int64_t N;
+  int32_t balls_per_episode; /* >= 1 */
+  int32_t reserved;
+} rth_game_args;
+/* env.reset() of every env at t = 0: state from Philox(seed, env, 0), stats = 0, the reset stack
+ * (the reset state's frame x4) into ring slot 1, cur_slot = 1.  frames_dev 16-byte aligned. */
+int rth_game_reset(const rth_game_args *game, uint8_t *frames_dev, int64_t n_actors, int32_t ring,
+                   int64_t *cur_slot_dev, void *stream);
+/* one game step per actor with the given actions (any int64: 0 and below stay, odd right, even
+ * left), the counterpart of rth_synth_env_step: reward in {-1, 0, +1}, done, handles, the shifted
+ * stack with the render of the state after the step (the terminal state on done) and, on done, the
+ * reset stack; the env is reset (Philox(seed, env, t)) and its stats row updated. */
+int rth_game_env_step(const rth_game_args *game, uint8_t *frames_dev, int64_t n_actors, int32_t ring, int64_t t,
+                      const int64_t *t_dev, int64_t *cur_slot_dev, const int64_t *action_dev, float *r_out_dev,
+                      float *done_out_dev, int64_t *s0_handle_dev, int64_t *s1_handle_dev, void *stream);
+/* rth_actor_tail with the game as the env (p_reward / p_done unused, ext_frames = 0): ε-greedy (or
+ * game->action_in; args->q may then be NULL), the previous rows' |td|, rth_game_env_step at
+ * t = *t_dev with the chosen action, rth_nstep_push; every value equals the one of those separate
+ * calls. */
+int rth_game_actor_tail(rth_nstep *h, const rth_actor_tail_args *args, const rth_game_args *game, int32_t *emit_dev,
+                        int64_t *s0_out_dev, int64_t *a_out_dev, float *r_out_dev, int64_t *s1_out_dev,
+                        float *done_out_dev, void *stream);
 /* stream compaction for variable-size device batches: out[0..k) = vals[i] for the i < n with
  * flag[i] != 0, in order of i (at most cap of them), out[k..cap) = fill, *count_out = base + k.
  * The actors use it to list the terminal stacks of the episodes that just ended (flag = done,

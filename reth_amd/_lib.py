@@ -82,6 +82,13 @@ class ActorTailArgs(ctypes.Structure):
                 ("s0_h", c_vp), ("s1_h", c_vp), ("seed", c_u64), ("N", c_i64), ("gamma_n", c_f32),
                 ("p_reward", c_f32), ("p_done", c_f32), ("ring", c_i32), ("A", c_i32), ("ext_frames", c_i32)]
 
+
+class GameArgs(ctypes.Structure):
+    """rth_game_args"""
+    _fields_ = [("state", c_vp), ("stats", c_vp), ("action_in", c_vp), ("seed", c_u64), ("N", c_i64),
+                ("balls_per_episode", c_i32), ("reserved", c_i32)]
+
+
 class MlpActorArgs(ctypes.Structure):
     """rth_mlp_actor_args"""
     _fields_ = [("params", ctypes.POINTER(c_vp)), ("D", c_i64), ("H", c_i64), ("A", c_i64), ("state", c_vp),
@@ -148,6 +155,12 @@ SIGNATURES = {
     "rth_synth_env_step": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_u64, c_f32, c_f32,
                                    c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rth_synth_env_reset": (c_i32, [c_vp, c_i64, c_i32, c_u64, c_vp, c_vp]),
+    # the Paddle game (game.hpp)
+    "rth_game_reset": (c_i32, [ctypes.POINTER(GameArgs), c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "rth_game_env_step": (c_i32, [ctypes.POINTER(GameArgs), c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp]),
+    "rth_game_actor_tail": (c_i32, [c_vp, ctypes.POINTER(ActorTailArgs), ctypes.POINTER(GameArgs), c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp]),
     # learner
     "rth_td_huber": (c_i32, [c_vp] * 7 + [c_i64, c_i64, c_f32, c_i32, c_i32] + [c_vp] * 5 + [c_vp]),
     "rth_bias_relu": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),

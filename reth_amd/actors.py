@@ -20,6 +20,9 @@ Here all N actors of a GPU step together, entirely in HBM:
            rth_actor_tail (eps-greedy + |td| + env step + n-step push, one launch)
   append(): rth_replay_append copies the rows' stacks from the ring into FIFO slots and
            inserts (|td| + 1e-6)^alpha into the tree.
+  env="paddle": the env step is the device-resident pixel game of csrc/game.hpp (rth_game_env_step /
+           rth_game_actor_tail; envs.Paddle is its host form) -- a real control problem on the
+           same frame ring, where the synthetic env's rewards ignore the action.
 No host synchronisation anywhere in the loop.
 """
 
@@ -32,6 +35,7 @@ from .solver import td_huber_forward
 
 OBS_SHAPE = (4, 84, 84)
 STACK_ELEMS = 4 * 84 * 84
+ENVS = ("synthetic", "atari", "atari-h2d", "paddle")
 
 
 def apex_epsilons(n, offset=0, total=None):
@@ -46,7 +50,9 @@ def apex_epsilons(n, offset=0, total=None):
 class VecActors:
     def __init__(self, n_actors, num_actions, n_step=3, gamma=0.99, device=None, seed=0, eps=None,
                  actor_offset=0, total_actors=None, p_reward=0.02, p_done=1.0 / 2000, nstep_mode=0,
-                 channels_last=False, env="synthetic"):
+                 channels_last=False, env="synthetic", balls_per_episode=5):
+        if env not in ENVS:
+            raise ValueError(f"env {env!r}: {' | '.join(ENVS)}")
         self.N = int(n_actors)
         self.A = int(num_actions)
         self.n_step, self.gamma = int(n_step), float(gamma)
@@ -108,7 +114,6 @@ class VecActors:
         self.t = 0           # env steps taken (per actor): host mirror of t_dev
         self.t_dev = torch.zeros(1, dtype=torch.int64, device=dev)  # what the kernels read
         self.pushes = 0
-        call("rth_synth_env_reset", ptr(self.frames), N, ring, self.seed, ptr(self.cur_slot), stream_ptr())
         self.frame_replay = None  # attach_frame_store: the frame de-duplicated replay the steps feed
         self.sid = None
         # env: "synthetic" -- Pong-shaped uint8 frames straight from device Philox;
@@ -116,11 +121,21 @@ class VecActors:
         # through the MaxAndSkip / WarpFrame / FrameStack preprocessing (rth_atari_env_step)
         # into the frame ring; "atari-h2d" -- the raw pairs copied host -> device from pinned
         # memory every step first, as from host ALE emulators (reth/reth/env/util.py:121-209).
-        # The reset screens of ended episodes come from device Philox in both modes
-        if env not in ("synthetic", "atari", "atari-h2d"):
-            raise ValueError(f"env {env!r}: synthetic | atari | atari-h2d")
+        # The reset screens of ended episodes come from device Philox in both modes;
+        # "paddle" -- the device-resident pixel game of csrc/game.hpp (envs.Paddle on the host):
+        # its state steps inside the actor launch, its frames are rendered straight into the
+        # ring, its reward and episode end follow from the action (p_reward / p_done are ignored)
         self.env = env
-        if env != "synthetic":
+        self.action_in = None  # paddle: int64 [N] device actions overriding the ε-greedy choice (tests, scripted play)
+        if env == "paddle":
+            self.balls_per_episode = int(balls_per_episode)
+            self.game_state = torch.zeros((N, 8), dtype=torch.int32, device=dev)
+            self.game_stats = torch.zeros((N, 4), dtype=torch.int64, device=dev)
+            g = self._game_args()
+            call("rth_game_reset", _lib.ctypes.byref(g), ptr(self.frames), N, ring, ptr(self.cur_slot), stream_ptr())
+        else:
+            call("rth_synth_env_reset", ptr(self.frames), N, ring, self.seed, ptr(self.cur_slot), stream_ptr())
+        if env in ("atari", "atari-h2d"):
             from .atari import AtariPreprocessor
 
             self.atari = AtariPreprocessor(device=dev)
@@ -141,6 +156,32 @@ class VecActors:
         self.frame_replay = replay
         self.sid = torch.zeros((self.frames.shape[0], OBS_SHAPE[0]), dtype=torch.int32, device=self.device)
         replay.push_frames(self.frames, self.N, self.ring, None, None, None, self.cur_slot, self.sid, init=True)
+
+    def _game_args(self):
+        return _lib.GameArgs(ptr(self.game_state), ptr(self.game_stats), ptr(self.action_in), self.seed, self.N,
+                             self.balls_per_episode, 0)
+
+    def _env_step(self, s):
+        """the env step as a launch of its own (step(), step_fused() without the HIP torso)"""
+        if self.env == "paddle":
+            if self.action_in is not None:
+                self.action.copy_(self.action_in)
+            g = self._game_args()
+            call("rth_game_env_step", _lib.ctypes.byref(g), ptr(self.frames), self.N, self.ring, 0, ptr(self.t_dev),
+                 ptr(self.cur_slot), ptr(self.action), ptr(self.reward), ptr(self.done), ptr(self.s0_h),
+                 ptr(self.s1_h), s)
+        else:
+            call("rth_synth_env_step", ptr(self.frames), self.N, self.ring, 0, ptr(self.t_dev), ptr(self.cur_slot),
+                 ptr(self.action), self.seed, self.p_reward, self.p_done, ptr(self.reward), ptr(self.done),
+                 ptr(self.s0_h), ptr(self.s1_h), s)
+
+    def episode_stats(self):
+        """paddle: per-env device statistics (int64 [N] each): finished episodes, the sum of their
+        returns, the last finished episode's return and its length"""
+        if self.env != "paddle":
+            raise RuntimeError("episode statistics are kept by the paddle env")
+        st = self.game_stats
+        return st[:, 0], st[:, 1], st[:, 2], st[:, 3]
 
     def _push_frames(self):
         if self.frame_replay is not None:
@@ -201,7 +242,7 @@ class VecActors:
     @torch.no_grad()
     def step(self, q_net):
         """one environment step for every actor; returns True when rows were emitted"""
-        if self.env != "synthetic":
+        if self.env in ("atari", "atari-h2d"):
             raise RuntimeError("the Atari env mode runs in step_fused with the HIP torso actor network")
         s = stream_ptr()
         self.t += 1
@@ -210,9 +251,7 @@ class VecActors:
         q, dueling = self._forward_stacks(q_net, self.current_obs_handles())
         call("rth_eps_greedy", ptr(q), self.N, self.A, dueling, ptr(self.eps), None, None, self.seed, 0,
              ptr(self.t_dev), ptr(self.action), s)
-        call("rth_synth_env_step", ptr(self.frames), self.N, self.ring, 0, ptr(self.t_dev), ptr(self.cur_slot),
-             ptr(self.action), self.seed, self.p_reward, self.p_done, ptr(self.reward), ptr(self.done), ptr(self.s0_h),
-             ptr(self.s1_h), s)
+        self._env_step(s)
         self._push_frames()
         call("rth_nstep_push", self._nstep, ptr(self.s0_h), ptr(self.action), ptr(self.reward), ptr(self.s1_h),
              ptr(self.done), ptr(self.emit), ptr(self.row_s0), ptr(self.row_a), ptr(self.row_r), ptr(self.row_s1),
@@ -307,8 +346,15 @@ class VecActors:
                                       ptr(prev.s0), ptr(prev.a), ptr(prev.s1), ptr(prev.r), ptr(prev.done),
                                       ptr(td_abs), ptr(self.frames), ptr(self.cur_slot), ptr(self.reward),
                                       ptr(self.done), ptr(self.s0_h), ptr(self.s1_h), self.seed, N, self.gamma_n,
-                                      self.p_reward, self.p_done, self.ring, self.A, int(self.env != "synthetic"))
-            def tail(args=args, cur=cur):
+                                      self.p_reward, self.p_done, self.ring, self.A,
+                                      int(self.env in ("atari", "atari-h2d")))
+            game = self._game_args() if self.env == "paddle" else None
+
+            def tail(args=args, cur=cur, game=game):
+                if game is not None:  # the game step in place of the synthetic env's (rth_game_actor_tail)
+                    call("rth_game_actor_tail", self._nstep, _lib.ctypes.byref(args), _lib.ctypes.byref(game),
+                         ptr(self.emit), ptr(cur.s0), ptr(cur.a), ptr(cur.r), ptr(cur.s1), ptr(cur.done), stream_ptr())
+                    return
                 call("rth_actor_tail", self._nstep, _lib.ctypes.byref(args), ptr(self.emit), ptr(cur.s0), ptr(cur.a),
                      ptr(cur.r), ptr(cur.s1), ptr(cur.done), stream_ptr())
 
@@ -316,7 +362,7 @@ class VecActors:
                 probe([("actor_tail", tail)])
             else:
                 tail()
-            if self.env != "synthetic":
+            if self.env in ("atari", "atari-h2d"):
                 self._atari_frames(s)
             self._push_frames()
             self._terminal_stacks()
@@ -325,7 +371,7 @@ class VecActors:
             self._bind_rows(cur)
             return (td_abs, prev) if p > self.n_step else (None, None)
         else:
-            if self.env != "synthetic":
+            if self.env in ("atari", "atari-h2d"):
                 raise RuntimeError("the Atari env mode runs with the HIP torso actor network (dueling, channels-last)")
             call("rth_counter_add", ptr(self.t_dev), 1, s)
             torch.cat([self.current_obs_handles(), prev.s0, prev.s1], out=self.handles3)
@@ -335,9 +381,7 @@ class VecActors:
              ptr(self.t_dev), ptr(self.action), s)
         _, td_abs, _ = td_huber_forward(q0, q1, q1, prev.a, prev.r, prev.done, None, self.gamma_n, True,
                                         want_dq=False, dueling=bool(dueling))
-        call("rth_synth_env_step", ptr(self.frames), N, self.ring, 0, ptr(self.t_dev), ptr(self.cur_slot),
-             ptr(self.action), self.seed, self.p_reward, self.p_done, ptr(self.reward), ptr(self.done), ptr(self.s0_h),
-             ptr(self.s1_h), s)
+        self._env_step(s)
         self._push_frames()
         call("rth_nstep_push", self._nstep, ptr(self.s0_h), ptr(self.action), ptr(self.reward), ptr(self.s1_h),
              ptr(self.done), ptr(self.emit), ptr(cur.s0), ptr(cur.a), ptr(cur.r), ptr(cur.s1), ptr(cur.done), s)

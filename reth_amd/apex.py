@@ -100,7 +100,8 @@ class ApexConfig:
     hip_conv: bool = True          # conv torso forward in rth_conv_bias_relu (actors/targets read uint8 stacks)
     dp_hook: Optional[bool] = None  # gradient all-reduce hook: None = when world > 1 (tests force it)
     tuned_gemm: bool = True        # TunableOp solution selection for the library GEMMs (reth_amd.gemm_tuning)
-    env: str = "synthetic"         # actors' observations: synthetic | atari | atari-h2d (VecActors)
+    env: str = "synthetic"         # actors' env: synthetic | atari | atari-h2d | paddle (VecActors)
+    balls_per_episode: int = 5     # env "paddle": balls per episode (p_reward / p_done are ignored there)
     frame_store: bool = False      # frame de-duplicated replay: each frame stored once, rows as frame ids
     frame_store_bound: str = "hard"  # store size: "hard" (worst case, 2 frames per actor step) | "expected" (p_done)
     frame_ids: bool = True         # frame store: batches hold frame ids, conv1 reads the frames in place (no stacks)
@@ -144,7 +145,8 @@ class ApexDQN:
         self.actors = VecActors(cfg.n_actors, cfg.num_actions, cfg.n_step, cfg.gamma, self.device,
                                 seed=cfg.seed * 1000003 + rank, actor_offset=rank * cfg.n_actors,
                                 total_actors=cfg.n_actors * world, p_reward=cfg.p_reward, p_done=cfg.p_done,
-                                nstep_mode=cfg.nstep_mode, channels_last=cfg.channels_last, env=cfg.env)
+                                nstep_mode=cfg.nstep_mode, channels_last=cfg.channels_last, env=cfg.env,
+                                balls_per_episode=cfg.balls_per_episode)
         self.svc, self.addr = start_per(cfg.capacity, cfg.batch_size, alpha=cfg.alpha, beta=cfg.beta,
                                         sample_start=cfg.sample_start, device=self.device, seed=cfg.seed + 7919 * rank)
         u8 = bool(cfg.hip_conv and cfg.channels_last)
@@ -181,12 +183,16 @@ class ApexDQN:
         n + 4).  "expected" sizes for
         the i.i.d. episode-end rate p_done instead -- capacity (1 + 2 p_done), at least
         capacity / 64 of headroom, + (n + 16) N: half the bytes, but a burst of episode ends
-        beyond that rate would overwrite frames that old rows still name."""
+        beyond that rate would overwrite frames that old rows still name.  The
+        paddle env's episodes end by its rules, not by p_done: an episode of b balls lasts at
+        least 25 b steps (a ball falls 75+ rows at no more than 3 a step), and that rate -- a
+        bound, not an expectation -- takes p_done's place."""
         if cfg.frame_store_bound == "hard":
             return 2 * cfg.capacity + 2 * (cfg.n_step + 16 + 2 * cfg.actor_steps_per_update) * cfg.n_actors + 16
         if cfg.frame_store_bound != "expected":
             raise ValueError(f"frame_store_bound {cfg.frame_store_bound!r}: 'hard' or 'expected'")
-        reset = max(cfg.capacity // 64, int(2 * cfg.capacity * cfg.p_done) + 1)
+        p_done = 1.0 / (25 * cfg.balls_per_episode) if cfg.env == "paddle" else cfg.p_done
+        reset = max(cfg.capacity // 64, int(2 * cfg.capacity * p_done) + 1)
         # + 8 N: the actors' initial stacks, pushed at construction and again behind a prefill
         return cfg.capacity + reset + (cfg.n_step + 16) * cfg.n_actors + 16
 
@@ -197,6 +203,44 @@ class ApexDQN:
             from . import gemm_tuning
 
             gemm_tuning.restore()
+
+    # ------------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def greedy_eval(self, n_envs=256, seed=12345, eps=0.0, action_fn=None):
+        """env "paddle": the mean return of the first episode of each of n_envs greedy (ε = 0)
+        envs of a separate actor set under the learner's current online network (a private copy
+        of its weights, taken now), from the device statistics.  Every env finishes its first
+        episode within 38 balls_per_episode steps; taking each env's first episode keeps short
+        episodes from counting more often than long ones.  One host read, at the end.
+        eps = 1.0 gives the random policy's return over the same envs.  action_fn(actors) ->
+        int64 [n_envs] device actions replaces the network's choice (scripted policies, tests)."""
+        cfg = self.cfg
+        if cfg.env != "paddle":
+            raise RuntimeError("greedy_eval plays the paddle env (ApexConfig.env = 'paddle')")
+        torch.cuda.synchronize(self.device)  # the learner's stream has finished the update whose weights are read
+        net = getattr(self, "_eval_net", None)
+        if net is None:
+            fmt = torch.channels_last if cfg.channels_last else torch.contiguous_format
+            net = self._eval_net = DQNNetwork(OBS_SHAPE, cfg.num_actions).to(self.device, memory_format=fmt)
+            net.requires_grad_(False)
+            net.hwc_features = bool(cfg.channels_last)
+            net.hip_conv = bool(cfg.hip_conv)
+        for dst, src in zip(net.parameters(), self.solver.q_network.parameters()):
+            dst.copy_(src)
+        net.freeze_heads()
+        ev = VecActors(n_envs, cfg.num_actions, cfg.n_step, cfg.gamma, self.device, seed=seed, eps=eps,
+                       channels_last=cfg.channels_last, env="paddle", balls_per_episode=cfg.balls_per_episode)
+        first = torch.zeros(ev.N, dtype=torch.int64, device=self.device)
+        got = torch.zeros(ev.N, dtype=torch.bool, device=self.device)
+        episodes, _, last, _ = ev.episode_stats()
+        for _ in range(38 * cfg.balls_per_episode):
+            if action_fn is not None:
+                ev.action_in = action_fn(ev)
+            ev.step(net)
+            new = (episodes > 0) & ~got
+            first = torch.where(new, last, first)
+            got |= new
+        return float((first.sum() / got.sum().clamp(min=1)).item())
 
     # ------------------------------------------------------------------ replay prefill
     @torch.no_grad()

@@ -11,6 +11,9 @@ the reference's wrapped env (env/util.py:281-297, wrap_deepmind + 4-frame stack:
 observations [4, 84, 84], the game's minimal action set) over synthetic frames with the
 bench's reward / episode-end rates -- a stand-in so the reference's scripts build their
 solver, trainer and workers; ALE emulation itself is out of scope.
+
+Paddle ("Paddle-v0") is a small real pixel game with the same observation interface, the host
+restatement of the device game the conv path's actors run (csrc/game.hpp).
 """
 import math
 
@@ -94,8 +97,93 @@ class SyntheticAtari:
         return self._stack.copy(), r, bool(u[1] < self.p_done), {}
 
 
+class Paddle:
+    """the host restatement of the device game of csrc/game.hpp (VecActors(env="paddle")): all
+    integer, so the two agree bit for bit when fed the same draws.
+
+    A ball (4x4, value 255) falls from the top with velocity (vx, vy), bouncing off the side
+    walls; the paddle (12x3, value 160, rows 78..80) moves 4 px per step: action 0 stays, odd
+    actions move right, even actions > 0 move left, clamped to [0, 72].  When the ball reaches
+    the paddle rows (ball_y + 4 > 78) it is resolved: reward +1 if it overlaps the paddle's
+    columns, else -1; after `balls_per_episode` balls the episode ends.  Observations are the
+    last four 84x84 uint8 frames (reset: the first frame four times, env/util.py:179-209); the
+    observation of a step is the render of the state after it -- the terminal state on done,
+    the new ball after a spawn.
+
+    state: int32[8] = ball_x, ball_y, vx, vy, paddle_x, balls_left, ep_return, ep_steps.
+    draw(env, t) -> three uint32 (c0, c1, c2) for the spawn at step t / the reset at step t
+    (t counts this object's step() calls and is not reset by reset(); the first reset is t = 0):
+    ball_x = (c0 * 81) >> 32, vx = VX[(c1 * 6) >> 32], vy = VY[(c2 * 2) >> 32].  The device
+    draws them from Philox(seed, env, t) on stream 8; the default here is a RandomState."""
+    W, BALL, PAD_W, PAD_H, PAD_Y, PAD_SPEED, PAD_START = 84, 4, 12, 3, 78, 4, 36
+    VX, VY = (-3, -2, -1, 1, 2, 3), (2, 3)
+
+    def __init__(self, num_actions=6, balls_per_episode=5, seed=None, draw=None, env=0):
+        if num_actions < 3 or balls_per_episode < 1:
+            raise ValueError("Paddle: num_actions >= 3 (stay / right / left), balls_per_episode >= 1")
+        self.observation_space = Box(0, 255, (4, self.W, self.W), np.uint8)
+        self.action_space = Discrete(int(num_actions))
+        self.balls_per_episode = int(balls_per_episode)
+        self.np_random = np.random.RandomState(seed)
+        self.draw = draw if draw is not None else self._draw
+        self.env = int(env)
+        self.t = 0
+        self.state = None
+        self._stack = None
+
+    def _draw(self, env, t):
+        return self.np_random.randint(0, 2 ** 32, 3, dtype=np.uint64).astype(np.uint32)
+
+    def _spawn(self):
+        c0, c1, c2 = (int(c) for c in self.draw(self.env, self.t))
+        self.state[0:4] = (c0 * (self.W - self.BALL + 1)) >> 32, 0, self.VX[(c1 * 6) >> 32], self.VY[(c2 * 2) >> 32]
+
+    def render(self, state=None):
+        """the 84x84 uint8 frame of a state (default: the current one); the ball over the paddle"""
+        bx, by, _, _, px = (int(v) for v in (self.state if state is None else state)[:5])
+        f = np.zeros((self.W, self.W), np.uint8)
+        f[self.PAD_Y:self.PAD_Y + self.PAD_H, px:px + self.PAD_W] = 160
+        f[by:by + self.BALL, bx:bx + self.BALL] = 255
+        return f
+
+    def reset(self):
+        self.state = np.zeros(8, np.int32)
+        self.state[4:8] = self.PAD_START, self.balls_per_episode, 0, 0
+        self._spawn()
+        self._stack = np.repeat(self.render()[None], 4, axis=0)
+        return self._stack.copy()
+
+    def step(self, action):
+        a = int(action)
+        assert 0 <= a < self.action_space.n, action
+        bx, by, vx, vy, px, balls, ret, steps = (int(v) for v in self.state)
+        px = min(max(px + (0 if a == 0 else (self.PAD_SPEED if a & 1 else -self.PAD_SPEED)), 0), self.W - self.PAD_W)
+        bx += vx
+        if bx < 0:
+            bx, vx = -bx, -vx
+        elif bx > self.W - self.BALL:
+            bx, vx = 2 * (self.W - self.BALL) - bx, -vx
+        by += vy
+        steps += 1
+        self.t += 1
+        reward, done = 0.0, False
+        resolved = by + self.BALL > self.PAD_Y
+        if resolved:
+            reward = 1.0 if (bx + self.BALL > px and bx < px + self.PAD_W) else -1.0
+            ret += int(reward)
+            balls -= 1
+            done = balls == 0
+        self.state[:] = bx, by, vx, vy, px, balls, ret, steps
+        if resolved and not done:
+            self._spawn()
+        self._stack = np.concatenate([self._stack[1:], self.render()[None]])
+        return self._stack.copy(), reward, done, {}
+
+
 def make(name, **kwargs):
     """reth.env.make (env/util.py:305-316) for the environments this build carries"""
+    if name == "Paddle-v0":
+        return Paddle(**kwargs)
     if name == "CartPole-v0":
         return CartPole(200, **kwargs)
     if name == "CartPole-v1":
@@ -104,5 +192,6 @@ def make(name, **kwargs):
     if name.endswith("NoFrameskip-v4") and name[: -len("NoFrameskip-v4")] in ATARI_ACTIONS:
         return SyntheticAtari(name[: -len("NoFrameskip-v4")], **kwargs)
     raise NotImplementedError(f"environment {name!r}: gym/ALE are not part of this build (CartPole-v0/v1 are "
-                              "restated, Atari names get SyntheticAtari; Atari observations: "
+                              "restated, Paddle-v0 is the device game's host form, Atari names get SyntheticAtari; "
+                              "Atari observations: "
                               "reth_amd.atari.AtariPreprocessor)")
