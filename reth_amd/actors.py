@@ -210,7 +210,7 @@ class VecActors:
         """Q-net over the frame-ring stacks `handles`: the HIP torso reads the uint8 ring
         directly (rth_conv_bias_relu through the handle index, no f32 copy); other networks
         get a u8 -> f32 gather first"""
-        if getattr(q_net, "hwc_features", False) and getattr(q_net, "dueling", False) and q_net.hip_conv:
+        if getattr(q_net, "hip_torso", False):
             return q_net.forward_heads(self.frames, rows=handles), 1
         n = handles.numel()
         buf = self._f32.get(n)
@@ -271,10 +271,6 @@ class VecActors:
         """the actor network was reloaded: cached heads are stale until n + 2 steps passed"""
         self.fresh = 0
 
-    @staticmethod
-    def _hip_heads(q_net):
-        return getattr(q_net, "hwc_features", False) and getattr(q_net, "dueling", False) and q_net.hip_conv
-
     def dedup_ready(self, q_net):
         """every stack a row prioritised now can reference has cached heads computed with the
         current weights: its s0 was acted at most n + 1 steps ago, its s1 was acted at most n
@@ -284,7 +280,7 @@ class VecActors:
         rewrites the s1 of the window's older rows to the terminal observation but leaves their
         done at 0, so those rows bootstrap from it (dropping the terminal forward was measured:
         |td| off in ~20 % of rows at p_done = 0.25, and no faster)"""
-        return self.qcache is not None and self.fresh >= self.n_step + 2 and self._hip_heads(q_net)
+        return self.qcache is not None and self.fresh >= self.n_step + 2 and getattr(q_net, "hip_torso", False)
 
     def _scatter_heads(self, q, handles, n):
         """qcache[handles[i]] = q[i] for i < n (the sink absorbs unused slots)"""
@@ -326,7 +322,7 @@ class VecActors:
             raise RuntimeError("step_fused(dedup=True): the stack cache is not valid for the current weights")
         self.t += 1
         N = self.N
-        hip = self._hip_heads(q_net)
+        hip = getattr(q_net, "hip_torso", False)
         if hip:  # step counter + acting rows (= cur_slot + _base) in one launch
             call("rth_actor_prologue", ptr(self.t_dev), ptr(self.cur_slot), N, self.ring, ptr(self.hx), s)
             if dedup:  # acting + terminal stacks (device count); the rows' heads are in the cache

@@ -403,7 +403,7 @@ class ApexDQN:
             # "full" runs them through the network (after a weights reload)
             act = self.actors
             fresh = act.fresh
-            modes = ["full"] + (["dedup"] if self.cfg.fused_actor and act._hip_heads(self.actor_net) else [])
+            modes = ["full"] + (["dedup"] if self.cfg.fused_actor and self.actor_net.hip_torso else [])
             G["act"], G["act_out"] = {}, {}
             for pr in psets:
                 for mode in modes:

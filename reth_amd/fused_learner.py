@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import call, ctypes, ptr, stream_ptr
 from . import model
-from .model import fc1_relu, nchw_out
+from .model import conv_workspace, fc1_relu
 from .replay import FrameStacks
 
 
@@ -58,29 +58,10 @@ DGRAD_MASK = True
 NORM_IN_BACKWARD = True
 
 
-def _net_workspace(net, kind, shape, device):
-    """a backward kernel's workspace, owned by the network: two learners in one process may
-    run (or replay) their backward passes on different streams, so no workspace is shared
-    between them -- rth_conv_dgrad_ws's packed flipped kernel, rth_conv_wgrad_{f32,x9}'s
-    split partials, rth_conv_relu_wgrad's conv1 partials; kind "fc1_bwd" (shape = (B, N, K)):
-    rth_fc_bwd's split partials, keyed by (device, B, N, K)"""
-    if kind == "fc1_bwd":
-        return model.fc1_bwd_workspace(net, device, *shape)
-    cache = net.__dict__.setdefault("_bwd_ws", {})
-    key = (device, kind, shape.input, shape.cin, shape.hin, shape.cout)
-    ws = cache.get(key)
-    if ws is None:
-        fn = {"dgrad": "rth_conv_dgrad_workspace", "conv1": "rth_conv_wgrad_workspace"}.get(
-            kind, f"rth_conv_wgrad_{kind}_workspace")
-        size = getattr(_lib.lib(), fn)(ctypes.byref(shape))
-        ws = cache[key] = torch.empty(max(size, 16) // 4, dtype=torch.float32, device=device)
-    return ws
-
-
 def eligible(net, s0, s1):
     """the explicit pass covers the channels-last dueling net whose three convs all run in
     rth_conv_bias_relu, on uint8 stacks or f32 channels-last observations"""
-    if not (getattr(net, "dueling", False) and getattr(net, "hwc_features", False) and getattr(net, "hip_conv", False)):
+    if not getattr(net, "hip_torso", False):
         return False
     frames = isinstance(s0, FrameStacks), isinstance(s1, FrameStacks)
     if any(frames):  # frames in place: conv1 reads the frame store by the batch's frame ids
@@ -144,7 +125,7 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
     with torch.no_grad():
         w1, b1, w2, b2 = net._merged_head_weights()  # FC1: the tied parameter storage
         hp = net._head_params()
-        fc2p = (_lib.c_vp * 4)(*[p.data_ptr() for p in hp[4:]])  # FC2 read in place
+        fc2p = net._fc2_ptrs(hp)[0]  # FC2 read in place
         # the packed data-gradient kernels of this iteration's weights (the backward reads the
         # same weights as the forward: the optimizer steps after both), packed in the forward's
         # pack launch
@@ -154,7 +135,7 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                 sh = shapes[li] if li < len(shapes) else None
                 if sh is None or _lib.lib().rth_conv_dgrad_workspace(ctypes.byref(sh)) <= 0:
                     continue
-                dgp[li] = _net_workspace(net, "dgrad", sh, x.device)
+                dgp[li] = conv_workspace(net, "dgrad", _lib.lib().rth_conv_dgrad_workspace, sh, x.device)
                 flagged = _lib.ConvShape(sh.input | _lib.CONV_PACK_DGRAD, sh.cin, sh.hin, sh.win, sh.cout, sh.kh, sh.kw,
                                          sh.stride)
                 extra.append((flagged, _nhwc(convs[li].weight.detach()).data_ptr(), dgp[li].data_ptr()))
@@ -163,20 +144,8 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
         ys, h = [], x
         probed = []  # [(tag, launch)] of conv2 / conv3, handed to probe together
         for li, (conv, shape) in enumerate(zip(convs, shapes)):
-            last = li == len(convs) - 1  # writes NCHW: FC1 reads the (C, H, W) flatten order
-            ho = (shape.hin - shape.kh) // shape.stride + 1
-            wo = (shape.win - shape.kw) // shape.stride + 1
-            y = torch.empty((n, shape.cout, ho, wo), dtype=torch.float32, device=x.device,
-                            memory_format=torch.contiguous_format if last else torch.channels_last)
-            def launch(shape=nchw_out(shape) if last else shape, h=h, pk=net._packed_for(packed, li, u8),
-                       b=conv.bias, y=y):
-                if isinstance(h, FrameStacks):
-                    call("rth_conv1_frames_bias_relu", ctypes.byref(shape), ptr(h.store), ptr(h.ids), n, ptr(pk),
-                         ptr(b), ptr(y), stream_ptr())
-                else:
-                    call("rth_conv_bias_relu", ctypes.byref(shape), ptr(h), None, n, ptr(pk), ptr(b), ptr(y),
-                         stream_ptr())
-
+            # the last conv writes NCHW: FC1 reads the (C, H, W) flatten order
+            y, launch = net._conv_launch(li, conv, shape, h, packed, li == len(convs) - 1)
             if probe is not None and li in (1, 2):
                 probed.append((f"conv{li + 1}", launch))
                 if li == min(2, len(convs) - 1):  # one cut for both: the prober issues them, in order
@@ -245,9 +214,7 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
         grads = {}
         deferred = []  # bias gradients whose slabs wait for conv1's reduce launch
         wdeferred = []  # conv2 / conv3 weight gradients whose partials wait for it (HIP_WGRAD "f32")
-        if getattr(net, "_ws", None) is None or net._ws[0].device != x.device:
-            net._ws = [torch.zeros(_lib.lib().rth_relu_bias_grad_workspace(m.out_channels), dtype=torch.uint8,
-                                   device=x.device) for m in convs]
+        rbws = net._relu_bias_ws(convs, x.device)
         fused_below = None  # (masked gradient, db) of the layer below, from the fused data gradient
         for li in range(len(convs) - 1, -1, -1):
             conv, y = convs[li], ys[li][:B]
@@ -259,7 +226,7 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                 assert len(deferred) <= 4, "rth_conv_relu_wgrad_ex finishes at most 4 deferred bias gradients"
                 jobs = (_lib.BiasDeferred * max(len(deferred), 1))(*deferred)
                 wjobs = (_lib.WgradDeferred * max(len(wdeferred), 1))(*wdeferred)
-                ws1 = _net_workspace(net, "conv1", shapes[0], x.device)
+                ws1 = conv_workspace(net, "conv1", _lib.lib().rth_conv_wgrad_workspace, shapes[0], x.device)
                 opt = solver.optimizer
                 if prenorm and NORM_IN_BACKWARD and mid is None and solver.grad_hook is None and hasattr(opt, "prenorm"):
                     # every gradient but conv1's weight and bias and the deferred biases (this
@@ -296,13 +263,13 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                 db = torch.empty(c, dtype=torch.float32, device=x.device)
                 if li == len(convs) - 1:  # NCHW output: mask + bias partials, gy written channels-last
                     call("rth_relu_bias_grad_nchw", ptr(g), ptr(y), ptr(gy), None if defer else ptr(db),
-                         ptr(net._ws[li]), nb, c, hh * ww, st)
+                         ptr(rbws[li]), nb, c, hh * ww, st)
                 else:
                     g = _nhwc(g)
-                    call("rth_relu_bias_grad", ptr(g), ptr(y), ptr(gy), None if defer else ptr(db), ptr(net._ws[li]),
+                    call("rth_relu_bias_grad", ptr(g), ptr(y), ptr(gy), None if defer else ptr(db), ptr(rbws[li]),
                          nb * hh * ww, c, st)
                 if defer:
-                    deferred.append(_lib.BiasDeferred(net._ws[li].data_ptr(), db.data_ptr(), nb * hh * ww, c, 0))
+                    deferred.append(_lib.BiasDeferred(rbws[li].data_ptr(), db.data_ptr(), nb * hh * ww, c, 0))
             xin = ys[li - 1][:B] if li > 0 else x[:B]
             w = _nhwc(conv.weight.detach())
             hip_dgrad = li in HIP_DGRAD and _lib.lib().rth_conv_dgrad_supported(ctypes.byref(shapes[li]))
@@ -316,7 +283,8 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
             if hip_wgrad:  # weight gradient in rth_conv_wgrad_{f32,x9} (deterministic, no zero fill)
                 gw = torch.empty(conv.weight.shape, dtype=torch.float32, device=x.device,
                                  memory_format=torch.channels_last)
-                ws = _net_workspace(net, HIP_WGRAD, shapes[li], x.device)
+                ws = conv_workspace(net, HIP_WGRAD, getattr(_lib.lib(), f"rth_conv_wgrad_{HIP_WGRAD}_workspace"),
+                                    shapes[li], x.device)
                 if HIP_WGRAD == "f32" and defer:  # partials now, the reduce in conv1's reduce launch
                     job = _lib.WgradDeferred()
                     call("rth_conv_wgrad_f32_partials", ctypes.byref(shapes[li]), ptr(xin), B, ptr(gy), ptr(gw), ptr(ws),
@@ -332,17 +300,17 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                     # + the layer below's ReLU mask and bias slabs (its rth_relu_bias_grad launch)
                     slabs = ctypes.c_int64(0)
                     call("rth_conv_dgrad_relu_prepacked", ctypes.byref(shapes[li]), ptr(gy), B, ptr(dgp[li]), ptr(xin),
-                         ptr(gx), ptr(net._ws[li - 1]), ctypes.byref(slabs), st)
+                         ptr(gx), ptr(rbws[li - 1]), ctypes.byref(slabs), st)
                     cb = convs[li - 1].out_channels
                     db_below = torch.empty(cb, dtype=torch.float32, device=x.device)
-                    deferred.append(_lib.BiasDeferred(net._ws[li - 1].data_ptr(), db_below.data_ptr(),
+                    deferred.append(_lib.BiasDeferred(rbws[li - 1].data_ptr(), db_below.data_ptr(),
                                                       xin.shape[0] * xin.shape[2] * xin.shape[3], cb, slabs.value))
                     fused_below = (gx, db_below)
                 elif li in dgp:  # packed in the forward's pack launch
                     call("rth_conv_dgrad_prepacked", ctypes.byref(shapes[li]), ptr(gy), B, ptr(dgp[li]), ptr(gx), st)
                 else:
-                    call("rth_conv_dgrad_ws", ctypes.byref(shapes[li]), ptr(gy), B, ptr(w), ptr(gx),
-                         ptr(_net_workspace(net, "dgrad", shapes[li], x.device)), st)
+                    ws = conv_workspace(net, "dgrad", _lib.lib().rth_conv_dgrad_workspace, shapes[li], x.device)
+                    call("rth_conv_dgrad_ws", ctypes.byref(shapes[li]), ptr(gy), B, ptr(w), ptr(gx), ptr(ws), st)
             grads[conv.weight], grads[conv.bias] = gw, db
             g = gx
         # every deferred bias gradient was finished by conv1's launch (else its db would be

@@ -9,8 +9,14 @@ reth/reth/algorithm/dqn/dqn_model.py:6-71, so
   * under the same torch.manual_seed the default initialisation is identical.
 """
 
+import copy
+
 import torch
 from torch import nn
+
+from . import _lib
+from ._lib import CONV_OUT_NCHW, ConvShape, c_vp, call, ctypes, lib, ptr, stream_ptr
+from .replay import FrameStacks
 
 
 def conv_out(size, k, s):
@@ -19,10 +25,46 @@ def conv_out(size, k, s):
 
 def nchw_out(shape):
     """a copy of an rth_conv_shape with RTH_CONV_OUT_NCHW set (the conv writes NCHW)"""
-    from ._lib import CONV_OUT_NCHW, ConvShape
-
     return ConvShape(shape.input | CONV_OUT_NCHW, shape.cin, shape.hin, shape.win, shape.cout, shape.kh, shape.kw,
                      shape.stride)
+
+
+def workspace(owner, device, kind, key, nbytes, zeroed_u8=False):
+    """the kernel workspace (device, kind, *key) of the network `owner`: max(nbytes, 16) // 4 float32
+    (zeroed_u8: nbytes zero-filled uint8) allocated on first use -- nbytes may be a callable giving
+    the size -- and the same tensor afterwards.  Every workspace lives in the one store
+    owner._workspaces and dies with its network: two networks in one process (two learners, the
+    actors' and the target's) run or replay on different streams and never share one, a replayed
+    graph sees a fixed address, and no module-level cache keyed by pointers can hand a later
+    network, allocated at a freed one's addresses, buffers from a released graph pool.  Without an
+    owner (tests and scripts calling fc1_relu / _LinearReLU directly) a fresh allocation per call."""
+    store = owner.__dict__.setdefault("_workspaces", {}) if owner is not None else {}
+    key = (device, kind, *key)
+    ws = store.get(key)
+    if ws is None:
+        if callable(nbytes):
+            nbytes = nbytes()
+        ws = store[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device) if zeroed_u8 else \
+            torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def conv_workspace(owner, kind, sizer, shape, device):
+    """a conv backward kernel's workspace of sizer(shape) bytes, keyed by kind, device and geometry:
+    "dgrad" rth_conv_dgrad_ws's packed flipped kernel, "f32" / "x9" rth_conv_wgrad_{f32,x9}'s split
+    partials, "conv1" rth_conv_relu_wgrad's conv1 partials"""
+    return workspace(owner, device, kind, (shape.input, shape.cin, shape.hin, shape.cout),
+                     lambda: sizer(ctypes.byref(shape)))
+
+
+def _copy_without(net, memo, skip):
+    """copy.deepcopy of a network without the per-object state named in skip"""
+    new = net.__class__.__new__(net.__class__)
+    memo[id(net)] = new
+    for k, v in net.__dict__.items():
+        if k not in skip:
+            new.__dict__[k] = copy.deepcopy(v, memo)
+    return new
 
 
 class DQNNetwork(nn.Module):
@@ -88,15 +130,9 @@ class DQNNetwork(nn.Module):
 
     def __deepcopy__(self, memo):
         """deepcopy clones every Parameter into its own storage: re-tie FC1 in the copy (the
-        cached head / packed weights are per-object state and are not carried over)"""
-        import copy
-
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        skip = ("_w1s", "_b1s", "_frozen", "_frozen_packed", "_ws", "_shape_cache", "_fc_ws", "_bwd_ws")
-        for k, v in self.__dict__.items():
-            if k not in skip:
-                new.__dict__[k] = copy.deepcopy(v, memo)
+        cached head / packed weights and the workspace store are per-object state and are not
+        carried over)"""
+        new = _copy_without(self, memo, ("_w1s", "_b1s", "_frozen", "_frozen_packed", "_shape_cache", "_workspaces"))
         if new.dueling:
             new._tie_heads()
         return new
@@ -150,15 +186,24 @@ class DQNNetwork(nn.Module):
         A, H = self.fc_adv[2].weight.shape
         return A <= 32 and H % 64 == 0 and H <= 512
 
+    @property
+    def hip_torso(self):
+        """the dueling network on channels-last activations whose convs run in rth_conv_bias_relu:
+        it reads uint8 stacks (through a row index, or a frame store) and returns raw heads"""
+        return bool(self.hwc_features and self.dueling and self.hip_conv)
+
+    def _fc2_ptrs(self, hp=None):
+        """(fc2_params, A, H) of the heads kernels: the pointers of the second layer's four parameters,
+        read in place (built per call: a parameter's storage may have moved).  hp: _head_params()
+        where the caller has them"""
+        ps = (hp or self._head_params())[4:]
+        return ((c_vp * 4)(*[p.data_ptr() for p in ps]), *ps[0].shape)
+
     def _heads_fc2(self, h):
         """the second layer on h = relu(FC1) [n, 2H] from the branch parameters in place
         (rth_heads_fc2): raw heads [n, A+1]"""
-        from ._lib import c_vp, call, ptr, stream_ptr
-
-        ps = self._head_params()[4:]
-        A, H = ps[0].shape
+        arr, A, H = self._fc2_ptrs()
         out = torch.empty((h.shape[0], A + 1), dtype=torch.float32, device=h.device)
-        arr = (c_vp * 4)(*[p.data_ptr() for p in ps])
         call("rth_heads_fc2", ptr(h), h.stride(0), h.shape[0], H, A, arr, ptr(out), stream_ptr())
         return out
 
@@ -167,21 +212,17 @@ class DQNNetwork(nn.Module):
         bias + ReLU and the second layer in one launch, r06; bit-identical to rth_fc_x9 +
         rth_heads_fc2) where built for the shape, else None.  h1_out (optional [n, 2H]) receives
         relu(FC1) (the learner's backward reads it)"""
-        from ._lib import c_vp, call, lib, ptr, stream_ptr
-
         if not (h.is_cuda and h.dim() == 2 and h.stride(1) == 1 and w1.is_contiguous() and self._fc2_inplace()):
             return None
         M, K = h.shape
         N = w1.shape[0]
-        ps = self._head_params()[4:]
-        A, H = ps[0].shape
+        arr, A, H = self._fc2_ptrs()
         if N != 2 * H or not lib().rth_fc1_heads_supported(M, N, K, A):
             return None
         out = torch.empty((M, A + 1), dtype=torch.float32, device=h.device)
-        arr = (c_vp * 4)(*[p.data_ptr() for p in ps])
-        ws = _fc_workspace("rth_fc_x9", h.device, w1, M, N, K, self)
-        call("rth_fc1_heads", ptr(h), h.stride(0), M, ptr(w1), N, K, ptr(b1), A, arr, ptr(out),
-             ptr(h1_out) if h1_out is not None else None, ptr(ws), stream_ptr())
+        ws = _fc_workspace(self, h.device, w1, M, N, K)
+        call("rth_fc1_heads", ptr(h), h.stride(0), M, ptr(w1), N, K, ptr(b1), A, arr, ptr(out), ptr(h1_out),
+             ptr(ws), stream_ptr())
         return out
 
     @torch.no_grad()
@@ -250,8 +291,6 @@ class DQNNetwork(nn.Module):
         a GEMM over the n_fixed live rows and rth_linear_relu_rows_upto over the counted rows
         behind them (usually none); then the second layer (+ the heads-cache scatter) over the
         counted rows only"""
-        from ._lib import c_vp, call, lib, ptr, stream_ptr
-
         n, F = h.shape
         O = w1.shape[0]
         if n_fixed is None:
@@ -263,16 +302,14 @@ class DQNNetwork(nn.Module):
             h1 = torch.empty((n, O), dtype=torch.float32, device=h.device)
             if w1.is_contiguous() and lib().rth_fc_x9_supported(n_fixed, O, F):
                 # the x9 GEMM over the fixed rows, then its split-K reduce and the counted rows in one launch
-                ws = _fc_workspace("rth_fc_x9", h.device, w1, n_fixed, O, F, self)
+                ws = _fc_workspace(self, h.device, w1, n_fixed, O, F)
                 call("rth_fc_x9_rows_upto", ptr(h), F, n_fixed, n, ptr(n_dev), ptr(w1), O, F, ptr(b1), ptr(h1), ptr(ws),
                      stream_ptr())
             else:  # (fixed rows not a multiple of 64: tiny actor counts) every counted row in HIP
                 call("rth_linear_relu_rows_upto", ptr(h), F, 0, n, ptr(n_dev), ptr(w1), ptr(b1), F, O, ptr(h1), O,
                      stream_ptr())
-        ps = self._head_params()[4:]
-        A, H = ps[0].shape
+        arr, A, H = self._fc2_ptrs()
         out = torch.empty((n, A + 1), dtype=torch.float32, device=h.device)
-        arr = (c_vp * 4)(*[p.data_ptr() for p in ps])
         qc, qrows = cache if cache is not None else (None, None)
         if qc is not None and (qc.shape[1] != A + 1 or qrows.numel() < n or qrows.dtype != torch.int64):
             raise ValueError("forward_heads: heads cache of the wrong width or too few cache rows")
@@ -298,8 +335,6 @@ class DQNNetwork(nn.Module):
         `out` (a previous result) is refilled in place.  `extra`: further (shape, weight
         pointer, buffer pointer) jobs packed in the same launch (the learner's data-gradient
         kernels, shape.input | CONV_PACK_DGRAD)."""
-        from . import _lib
-
         convs = self._convs()
         dev = convs[0].weight.device
         res = [] if out is None else out
@@ -339,67 +374,78 @@ class DQNNetwork(nn.Module):
             return packed[3]
         return packed[li]
 
+    def _relu_bias_ws(self, convs, device):
+        """per conv of convs = self._convs(): rth_relu_bias_grad's slab workspace (uint8, zero-filled
+        at creation)"""
+        return [workspace(self, device, "relu_bias_grad", (li,),
+                          lambda m=m: lib().rth_relu_bias_grad_workspace(m.out_channels), zeroed_u8=True)
+                for li, m in enumerate(convs)]
+
+    def _conv_launch(self, li, conv, shape, x, packed, last, rows=None, n_dev=None):
+        """conv = self._convs()[li] (+ bias + ReLU) on the HIP torso: (y, launch) -- the output [n, cout, ho, wo],
+        contiguous NCHW when `last` (shape flagged nchw_out: FC1 reads the (C, H, W) flatten order),
+        channels-last otherwise, and the zero-argument launch that fills it on the current stream.
+        x: a FrameStacks (rth_conv1_frames_bias_relu), else a tensor read through `rows` if given:
+        rth_conv_bias_relu_upto with a device count n_dev, else rth_conv_bias_relu.  The caller
+        decides `last`: the explicit learner pass and the counted actors' pass flag the final conv,
+        the autograd pass flags it only if li > 0 (a single conv stays channels-last there) and the
+        frames-in-place conv1 of inference never does."""
+        n = rows.numel() if rows is not None else x.shape[0]
+        y = torch.empty((n, shape.cout, conv_out(shape.hin, shape.kh, shape.stride),
+                         conv_out(shape.win, shape.kw, shape.stride)), dtype=torch.float32, device=x.device,
+                        memory_format=torch.contiguous_format if last else torch.channels_last)
+        shape = nchw_out(shape) if last else shape
+        pk, b = self._packed_for(packed, li, x.dtype == torch.uint8), conv.bias
+
+        def launch():
+            if isinstance(x, FrameStacks):
+                call("rth_conv1_frames_bias_relu", ctypes.byref(shape), ptr(x.store), ptr(x.ids), n, ptr(pk), ptr(b),
+                     ptr(y), stream_ptr())
+            elif n_dev is not None:
+                call("rth_conv_bias_relu_upto", ctypes.byref(shape), ptr(x), ptr(rows), n, ptr(n_dev), ptr(pk), ptr(b),
+                     ptr(y), stream_ptr())
+            else:
+                call("rth_conv_bias_relu", ctypes.byref(shape), ptr(x), ptr(rows), n, ptr(pk), ptr(b), ptr(y),
+                     stream_ptr())
+
+        return y, launch
+
     def _features_nhwc(self, x, rows=None, packed=None, n_dev=None):
         """the conv torso on channels-last activations: each Conv2d -> ReLU is one HIP
-        implicit-GEMM launch with the bias and ReLU fused (rth_conv_bias_relu) where the
+        implicit-GEMM launch with the bias and ReLU fused (_conv_launch) where the
         geometry is built, else MIOpen + the rth_bias_relu pass; the last HIP conv writes its
         output NCHW (FC1 reads the reference's (C, H, W) flatten order); backward:
         rth_relu_bias_grad(_nchw) and MIOpen's data/weight gradients"""
-        from . import _lib
-        from .replay import FrameStacks
-
-        if isinstance(x, FrameStacks) and (rows is not None or n_dev is not None or (
-                torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+        grad = lambda: torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if isinstance(x, FrameStacks) and (rows is not None or n_dev is not None or grad()):
             x = x.stacks()  # (frames in place is inference / the explicit learner pass only)
         u8 = x.dtype == torch.uint8
         if not u8 and not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
         convs = self._convs()
-        if getattr(self, "_ws", None) is None or self._ws[0].device != x.device:
-            self._ws = [torch.zeros(_lib.lib().rth_relu_bias_grad_workspace(m.out_channels), dtype=torch.uint8,
-                                    device=x.device) for m in convs]
-        shapes = self._torso_shapes(x.shape[1:], u8)
-        if packed is None and any(s is not None for _, s in shapes):
+        wss = self._relu_bias_ws(convs, x.device)
+        shapes = [sh for _, sh in self._torso_shapes(x.shape[1:], u8)]
+        if packed is None and any(sh is not None for sh in shapes):
             packed = self.pack_convs(u8)
         if n_dev is not None:  # device-counted inference batch: every layer in rth_conv_bias_relu_upto
-            from ._lib import call, ptr, stream_ptr
-
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if grad():
                 raise RuntimeError("forward_heads(n_dev=...) is inference only (no autograd)")
-            if any(sh is None for _, sh in shapes):
+            if any(sh is None for sh in shapes):
                 raise ValueError("forward_heads(n_dev=...) needs every conv in rth_conv_bias_relu")
-            n = rows.numel() if rows is not None else x.shape[0]
-            for li, conv in enumerate(convs):
-                shape = shapes[li][1]
-                last = li == len(convs) - 1
-                ho = (shape.hin - shape.kh) // shape.stride + 1
-                wo = (shape.win - shape.kw) // shape.stride + 1
-                y = torch.empty((n, shape.cout, ho, wo), dtype=torch.float32, device=x.device,
-                                memory_format=torch.contiguous_format if last else torch.channels_last)
-                call("rth_conv_bias_relu_upto", _lib.ctypes.byref(nchw_out(shape) if last else shape), ptr(x),
-                     ptr(rows) if li == 0 else None, n, ptr(n_dev), ptr(self._packed_for(packed, li, u8)),
-                     ptr(conv.bias), ptr(y), stream_ptr())
-                x = y
-            return x
-        for li, (conv, ws) in enumerate(zip(convs, self._ws)):
-            shape = shapes[li][1]
-            if isinstance(x, FrameStacks):  # conv1 from the frame store (no autograd: checked above)
-                from ._lib import call, ptr, stream_ptr
-
+        for li, (conv, shape, ws) in enumerate(zip(convs, shapes, wss)):
+            last = li == len(convs) - 1
+            if n_dev is not None or isinstance(x, FrameStacks):  # (frames: conv1, no autograd -- checked above)
                 if shape is None:
                     raise ValueError("frame-id batches need rth_conv_bias_relu's conv1 geometry")
-                y = torch.empty((x.shape[0], shape.cout, (shape.hin - shape.kh) // shape.stride + 1,
-                                 (shape.win - shape.kw) // shape.stride + 1), dtype=torch.float32, device=x.device,
-                                memory_format=torch.channels_last)
-                call("rth_conv1_frames_bias_relu", _lib.ctypes.byref(shape), ptr(x.store), ptr(x.ids), x.shape[0],
-                     ptr(self._packed_for(packed, li, u8)), ptr(conv.bias), ptr(y), stream_ptr())
-                x = y
-                continue
-            if shape is not None:
-                pk = self._packed_for(packed, li, u8)
-                last = li == len(convs) - 1 and li > 0  # the last conv writes NCHW (FC1's flatten order)
-                x = _HipConvBiasReLU.apply(x, conv.weight, conv.bias, pk, nchw_out(shape) if last else shape,
-                                           conv.stride, ws, rows if li == 0 else None)
+                x, launch = self._conv_launch(li, conv, shape, x, packed, last and n_dev is not None,
+                                              rows if li == 0 else None, n_dev)
+                launch()
+            elif shape is not None:
+                # conv1's weight gradient straight from uint8 stacks: rth_conv_relu_wgrad's partials
+                wws = conv_workspace(self, "conv1", lib().rth_conv_wgrad_workspace, shape, x.device) \
+                    if x.dtype == torch.uint8 and torch.is_grad_enabled() and conv.weight.requires_grad else None
+                x = _HipConvBiasReLU.apply(x, conv.weight, conv.bias, self, li, conv, shape, packed, last and li > 0,
+                                           ws, rows if li == 0 else None, wws)
             else:
                 if x.dtype == torch.uint8 or (li == 0 and rows is not None):
                     raise ValueError("uint8 / row-indexed observations need rth_conv_bias_relu's conv1 geometry")
@@ -408,20 +454,16 @@ class DQNNetwork(nn.Module):
 
     def _conv_shapes(self, x_shape, u8):
         """per conv: (None, rth_conv_shape or None when MIOpen runs it)"""
-        from . import _lib
-
         out = []
         c, h, w = x_shape
-        for li, conv in enumerate(m for m in self.features if isinstance(m, nn.Conv2d)):
+        for li, conv in enumerate(self._convs()):
             kind = _lib.CONV_U8_CHW if (u8 and li == 0) else _lib.CONV_F32_NHWC
-            shp = _lib.ConvShape(kind, c, h, w, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1],
-                                 conv.stride[0])
+            shp = ConvShape(kind, c, h, w, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0])
             ok = (self.hip_conv and conv.stride[0] == conv.stride[1] and conv.padding == (0, 0)
-                  and conv.dilation == (1, 1) and conv.groups == 1
-                  and _lib.lib().rth_conv_supported(_lib.ctypes.byref(shp)) == 1)
+                  and conv.dilation == (1, 1) and conv.groups == 1 and lib().rth_conv_supported(ctypes.byref(shp)) == 1)
             out.append((None, shp if ok else None))
-            c, h, w = conv.out_channels, (h - conv.kernel_size[0]) // conv.stride[0] + 1, \
-                (w - conv.kernel_size[1]) // conv.stride[1] + 1
+            c, h, w = conv.out_channels, conv_out(h, conv.kernel_size[0], conv.stride[0]), \
+                conv_out(w, conv.kernel_size[1], conv.stride[1])
         return out
 
 
@@ -431,8 +473,6 @@ class _MergeHeads(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dims, *ps):
-        from ._lib import c_vp, call, ptr, stream_ptr
-
         H, F, A, C, P = dims
         ps = [p.contiguous() for p in ps]
         o = dict(device=ps[0].device, dtype=torch.float32)
@@ -446,8 +486,6 @@ class _MergeHeads(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gw1, gb1, gw2, gb2):
-        from ._lib import c_vp, call, ptr, stream_ptr
-
         H, F, A, C, P = ctx.dims
         outs = [gw1, gb1, gw2, gb2]
         shapes = [(2 * H, F), (2 * H,), (A + 1, 2 * H), (A + 1,)]
@@ -469,9 +507,7 @@ class _MergeHeads(torch.autograd.Function):
 # which made the end-to-end |td| 2.1x the reference fp32 run's distance from the exact |td|; on
 # x9 it is 1.1x.  Cost in the loop: 0.516 -> 0.520 ms/step (interleaved, 3 rounds,
 # profiles/r06/ab_log.txt).
-_FC_WS = {}
-
-
+#
 # FC1_HEADS -- FC1's split-K reduce and FC2 in one launch (rth_fc1_heads) wherever the heads are
 # computed without autograd: the target pass and the learner's forward (r06); tests patch it
 FC1_HEADS = True
@@ -490,23 +526,14 @@ FC1_BWD = None
 MLP_IMPL = None
 
 
-def _fc_workspace(fn, device, w, M, N, K, owner=None):
-    """the split-K workspace of fn for (M, N, K), owned by the network that runs it (`owner`: its
-    workspaces live and die with it -- a module-level cache keyed by pointers would hand a later
-    network, allocated at a freed one's addresses, buffers from a released graph pool) and keyed
-    by the launching stream: the same network may run the same shape on two streams at once (the
+def _fc_workspace(owner, device, w, M, N, K):
+    """rth_fc_x9's split-K workspace for (M, N, K), keyed by the weight storage and by the
+    launching stream: the same network may run the same shape on two streams at once (the
     target network's B-row pass: the learner's own after a target sync on the learner stream,
     the next batch's on the actor stream), and a shared workspace would mix the two launches'
     split-K partials"""
-    from ._lib import lib, stream_ptr
-
-    cache = owner.__dict__.setdefault("_fc_ws", {}) if owner is not None else _FC_WS
-    key = (device, w.data_ptr(), M, N, K, fn, stream_ptr())
-    ws = cache.get(key)
-    if ws is None:
-        ws = cache[key] = torch.empty(max(getattr(lib(), fn + "_workspace")(M, N, K), 16) // 4, dtype=torch.float32,
-                                      device=device)
-    return ws
+    return workspace(owner, device, "rth_fc_x9", (w.data_ptr(), M, N, K, stream_ptr()),
+                     lambda: lib().rth_fc_x9_workspace(M, N, K))
 
 
 def fc1_relu(x, w, b, out=None, owner=None):
@@ -517,11 +544,9 @@ def fc1_relu(x, w, b, out=None, owner=None):
     M, K = x.shape
     N = w.shape[0]
     if x.is_cuda and x.stride(1) == 1 and w.is_contiguous():
-        from ._lib import call, lib, ptr, stream_ptr
-
         if lib().rth_fc_x9_supported(M, N, K):
             y = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=x.device)
-            ws = _fc_workspace("rth_fc_x9", x.device, w, M, N, K, owner)
+            ws = _fc_workspace(owner, x.device, w, M, N, K)
             call("rth_fc_x9", ptr(x), x.stride(0), M, ptr(w), N, K, ptr(b), 1, ptr(y), ptr(ws), stream_ptr())
             return y
     if out is not None:
@@ -529,32 +554,13 @@ def fc1_relu(x, w, b, out=None, owner=None):
     return torch._addmm_activation(b, x, w.t())
 
 
-def fc1_bwd_workspace(owner, device, B, N, K):
-    """rth_fc_bwd's workspace for (B, N, K): the entry (device, "fc1_bwd", B, N, K) of the owning
-    network's backward workspaces (net._bwd_ws, fused_learner._net_workspace); without an owner a
-    fresh allocation"""
-    from ._lib import lib
-
-    cache = owner.__dict__.setdefault("_bwd_ws", {}) if owner is not None else {}
-    key = (device, "fc1_bwd", B, N, K)
-    ws = cache.get(key)
-    if ws is None:
-        ws = cache[key] = torch.empty(max(lib().rth_fc_bwd_workspace(B, N, K), 16) // 4, dtype=torch.float32,
-                                      device=device)
-    return ws
-
-
 def fc1_backward(gy, x, w, want_gx=True, want_gw=True, owner=None):
     """FC1's backward on rth_fc_bwd: (gx = gy @ w or None, gw = gy.T @ x or None) from the masked
     output gradient gy [B, N], the input x [B, K] and the weight w [N, K]; None where FC1_BWD is
     not "hip" or the shape / layout is not built (the caller then runs the library GEMMs).  The
-    workspace is owned by the network that runs it (`owner`: its _bwd_ws, kind "fc1_bwd", keyed by
-    (device, B, N, K) -- two learners never share one and graph replays see a fixed address);
-    without an owner it is allocated per call."""
+    split partials' workspace is the owning network's, kind "fc1_bwd", keyed by (B, N, K)."""
     if FC1_BWD != "hip" or not (want_gx or want_gw) or not gy.is_cuda:
         return None
-    from ._lib import call, lib, ptr, stream_ptr
-
     (B, N), K = gy.shape, w.shape[1]
     if not lib().rth_fc_bwd_supported(B, N, K):
         return None
@@ -562,8 +568,8 @@ def fc1_backward(gy, x, w, want_gx=True, want_gw=True, owner=None):
     if any(t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16 for t in ts) \
             or not w.is_contiguous():
         return None
-    ws = fc1_bwd_workspace(owner, gy.device, B, N, K)
-    gx =torch.empty((B, K), dtype=torch.float32, device=gy.device) if want_gx else None
+    ws = workspace(owner, gy.device, "fc1_bwd", (B, N, K), lambda: lib().rth_fc_bwd_workspace(B, N, K))
+    gx = torch.empty((B, K), dtype=torch.float32, device=gy.device) if want_gx else None
     gw = torch.empty((N, K), dtype=torch.float32, device=gy.device) if want_gw else None
     call("rth_fc_bwd", ptr(gy), gy.stride(0), ptr(x) if want_gw else None, x.stride(0) if want_gw else 0,
          ptr(w) if want_gx else None, B, N, K, ptr(gx), ptr(gw), ptr(ws), stream_ptr())
@@ -604,8 +610,6 @@ class _ConvBiasReLU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, stride, ws):
-        from ._lib import call, ptr, stream_ptr
-
         y = torch.ops.aten.convolution(x, w, None, list(stride), [0, 0], [1, 1], False, [0, 0], 1)
         if not y.is_contiguous(memory_format=torch.channels_last):
             y = y.contiguous(memory_format=torch.channels_last)
@@ -617,8 +621,6 @@ class _ConvBiasReLU(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from ._lib import call, ptr, stream_ptr
-
         x, w, y = ctx.saved_tensors
         if not g.is_contiguous(memory_format=torch.channels_last):
             g = g.contiguous(memory_format=torch.channels_last)
@@ -631,54 +633,24 @@ class _ConvBiasReLU(torch.autograd.Function):
         return gx, gw, db, None, None
 
 
-_WGRAD_WS = {}
-
-
-def _wgrad_workspace(shape, device):
-    """rth_conv_relu_wgrad's partial-sum workspace (one per device; backward passes on a
-    device run in stream order)"""
-    from ._lib import ctypes, lib
-
-    key = (device, shape.input, shape.cin, shape.cout)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        nbytes = lib().rth_conv_wgrad_workspace(ctypes.byref(shape))
-        ws = _WGRAD_WS[key] = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=device)
-    return ws
-
-
 class _HipConvBiasReLU(torch.autograd.Function):
-    """relu(conv2d(x, w) + b) as one rth_conv_bias_relu launch (conv.hip); x channels-last
-    fp32, or uint8 CHW frame stacks (optionally through a row index) for the first layer.
-    Backward as _ConvBiasReLU: rth_relu_bias_grad + MIOpen data/weight gradients (a uint8
-    input is widened to the f32 channels-last batch it stands for)."""
+    """relu(conv2d(x, w) + b) as one rth_conv_bias_relu launch (net._conv_launch of layer li); x
+    channels-last fp32, or uint8 CHW frame stacks (optionally through a row index) for the first
+    layer.  Backward as _ConvBiasReLU: rth_relu_bias_grad + MIOpen data/weight gradients (a uint8
+    input is widened to the f32 channels-last batch it stands for), or with wgrad_ws (the
+    network's rth_conv_relu_wgrad workspace) conv1's gradients straight from the uint8 stacks."""
 
     @staticmethod
-    def forward(ctx, x, w, b, packed, shape, stride, ws, rows):
-        from ._lib import call, ctypes, ptr, stream_ptr
-
-        from ._lib import CONV_OUT_NCHW
-
-        n = rows.numel() if rows is not None else x.shape[0]
-        ho = (shape.hin - shape.kh) // shape.stride + 1
-        wo = (shape.win - shape.kw) // shape.stride + 1
-        nchw = bool(shape.input & CONV_OUT_NCHW)
-        y = torch.empty((n, shape.cout, ho, wo), dtype=torch.float32, device=x.device,
-                        memory_format=torch.contiguous_format if nchw else torch.channels_last)
-        call("rth_conv_bias_relu", ctypes.byref(shape), ptr(x), ptr(rows), n, ptr(packed), ptr(b), ptr(y),
-             stream_ptr())
+    def forward(ctx, x, w, b, net, li, conv, shape, packed, nchw, ws, rows, wgrad_ws):
+        y, launch = net._conv_launch(li, conv, shape, x, packed, nchw, rows)
+        launch()
         ctx.nchw = nchw
         ctx.save_for_backward(x, w, y, rows)
-        ctx.stride, ctx.ws, ctx.shape = list(stride), ws, shape
-        ctx.wgrad_ws = None
-        if x.dtype == torch.uint8 and ctx.needs_input_grad[1]:
-            ctx.wgrad_ws = _wgrad_workspace(shape, x.device)
+        ctx.stride, ctx.ws, ctx.shape, ctx.wgrad_ws = list(conv.stride), ws, shape, wgrad_ws
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from ._lib import call, ptr, stream_ptr
-
         x, w, y, rows = ctx.saved_tensors
         fmt = torch.contiguous_format if ctx.nchw else torch.channels_last
         if not g.is_contiguous(memory_format=fmt):
@@ -686,14 +658,12 @@ class _HipConvBiasReLU(torch.autograd.Function):
         if x.dtype == torch.uint8 and ctx.wgrad_ws is not None:
             # conv1 on uint8 stacks: ReLU mask + weight and bias gradients in one HIP pass
             # (rth_conv_relu_wgrad), straight from the stacks
-            from ._lib import ctypes
-
             gw = torch.empty(w.shape, dtype=w.dtype, device=w.device, memory_format=torch.channels_last)
             db = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
             n = y.shape[0]
             call("rth_conv_relu_wgrad", ctypes.byref(ctx.shape), ptr(x), ptr(rows), n, ptr(g), ptr(y), ptr(gw),
                  ptr(db), ptr(ctx.wgrad_ws), stream_ptr())
-            return None, gw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None
+            return (None, gw if ctx.needs_input_grad[1] else None, db) + (None,) * 9
         if not w.is_contiguous(memory_format=torch.channels_last):
             w = w.contiguous(memory_format=torch.channels_last)
         if x.dtype == torch.uint8:
@@ -708,7 +678,7 @@ class _HipConvBiasReLU(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0]
         gx, gw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, ctx.stride, [0, 0], [1, 1], False, [0, 0], 1,
                                                         [need_x, ctx.needs_input_grad[1], False])
-        return gx, gw, db, None, None, None, None, None
+        return (gx, gw, db) + (None,) * 9
 
 
 class MLP_DQNNetwork(nn.Module):
@@ -734,29 +704,24 @@ class MLP_DQNNetwork(nn.Module):
 
     def hip_supported(self):
         """the fused kernels are built for this shape and can read the parameters where they are"""
-        from ._lib import lib
-
         ps = self._params6()
         D, H, A = self.dims()
         return (all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps)
                 and self.nn[2].in_features == H and self.nn[4].in_features == H
                 and lib().rth_mlp_supported(D, H, A) == 1)
 
-    def _mlp_workspace(self, device, B):
-        """rth_mlp_dqn_grads' workspace for B rows, owned by this network and keyed by (device, B)
-        (like fused_learner._net_workspace: two solvers never share one, a replayed graph sees a
-        fixed address)"""
-        from ._lib import lib
+    def __deepcopy__(self, memo):
+        return _copy_without(self, memo, ("_workspaces",))
 
-        cache = self.__dict__.setdefault("_mlp_ws", {})
-        key = (device, int(B))
-        ws = cache.get(key)
-        if ws is None:
-            size = lib().rth_mlp_workspace(int(B), *self.dims())
-            if size <= 0:
+    def _mlp_workspace(self, device, B):
+        """rth_mlp_dqn_grads' workspace for B rows, owned by this network and keyed by (device, B)"""
+        def size():
+            nbytes = lib().rth_mlp_workspace(int(B), *self.dims())
+            if nbytes <= 0:
                 raise ValueError(f"rth_mlp_workspace: unsupported shape B={B} (D, H, A)={self.dims()}")
-            ws = cache[key] = torch.empty(size // 4, dtype=torch.float32, device=device)
-        return ws
+            return nbytes
+
+        return workspace(self, device, "mlp", (int(B),), size)
 
 
 def make_q_network(obs_shape, num_actions, dueling=True):

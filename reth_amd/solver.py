@@ -232,10 +232,8 @@ class DQNSolver(Algorithm):
         return fr(s0), f(a, torch.int64), f(r, torch.float32), fr(s1), f(done, torch.float32)
 
     def _u8_frames(self, x):
-        net = self.q_network
         return ((torch.is_tensor(x) or isinstance(x, FrameStacks)) and x.dtype == torch.uint8 and x.is_cuda
-                and self._heads
-                and getattr(net, "hwc_features", False) and getattr(net, "hip_conv", False))
+                and self._heads and getattr(self.q_network, "hip_torso", False))
 
     def target_heads(self, s1):
         """the target network's output on s1 (raw dueling heads with the HIP TD kernel): a
@@ -359,7 +357,7 @@ class DQNSolver(Algorithm):
         if self._heads:  # merged dueling head weights (and packed conv weights of the HIP torso),
             # built once per weight version and shared by both online passes
             merged = self.q_network._merged_head_weights()
-            if getattr(self.q_network, "hwc_features", False) and merged[0].is_cuda:
+            if getattr(self.q_network, "hip_torso", False) and merged[0].is_cuda:
                 with torch.no_grad():
                     packed = self.q_network.pack_convs()
             q0 = self.q_network.forward_heads(s0, merged, packed=packed)

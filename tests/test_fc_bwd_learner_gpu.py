@@ -38,7 +38,7 @@ def test_fc1_bwd_switch_reaches_the_learner(dev, monkeypatch, switch):
     torch.cuda.synchronize()
     assert ax.updates >= 1
     net = ax.solver.q_network
-    kinds = {k[1] for k in net.__dict__.get("_bwd_ws", {})}
+    kinds = {k[1] for k in net.__dict__.get("_workspaces", {})}
     assert ("fc1_bwd" in kinds) == (switch == "hip"), kinds
     assert all(torch.isfinite(p.grad).all() for p in net.parameters())
     ax.close()

@@ -168,6 +168,31 @@ def test_nhwc_features_forward_backward_match_module(dev):
         assert err < 1e-5, (name, err)
 
 
+def test_workspaces_belong_to_one_network(dev):
+    """every kernel workspace lives in the store of the network that runs the kernel: two networks
+    through the autograd path on uint8 stacks (conv1's weight gradient on rth_conv_relu_wgrad)
+    share no buffer, and a deep copy starts with an empty store and computes the same heads"""
+    import copy
+
+    from reth_amd.model import DQNNetwork
+
+    torch.manual_seed(5)
+    x = torch.randint(0, 256, (2, 4, 84, 84), dtype=torch.uint8, device=dev)
+    nets = [DQNNetwork((4, 84, 84), 3).to(dev, memory_format=torch.channels_last) for _ in range(2)]
+    for net in nets:
+        net.hwc_features = True
+        net.forward_heads(x).square().sum().backward()
+        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
+    stores = [net.__dict__["_workspaces"] for net in nets]
+    assert any(k[1] == "conv1" for k in stores[0]), list(stores[0])  # rth_conv_relu_wgrad ran
+    ptrs = [{t.data_ptr() for t in st.values()} for st in stores]
+    assert all(len(p) == len(st) > 0 for p, st in zip(ptrs, stores)) and not (ptrs[0] & ptrs[1])
+    twin = copy.deepcopy(nets[0])
+    assert not twin.__dict__.get("_workspaces")
+    with torch.no_grad():
+        assert torch.equal(twin.forward_heads(x), nets[0].forward_heads(x))
+
+
 def _make_solver(dev, seed, **kw):
     from reth_amd.solver import Box, DQNSolver, Discrete
 

@@ -61,6 +61,20 @@ def test_freeze_heads_refills_in_place():
     assert net._frozen[0].data_ptr() == net.fc_adv[0].weight.data_ptr()  # FC1: the tied storage
 
 
+def test_no_module_level_workspace_cache():
+    """kernel workspaces belong to the network that runs the kernel (model.workspace), never to the
+    module; a deep copy of either network class starts without any"""
+    import copy
+
+    from reth_amd import model
+
+    assert not hasattr(model, "_FC_WS") and not hasattr(model, "_WGRAD_WS")
+    for net in (DQNNetwork((4, 84, 84), 6), MLP_DQNNetwork((4,), 2)):
+        ws = model.workspace(net, torch.device("cpu"), "probe", (1,), 64)
+        assert ws.numel() == 16 and model.workspace(net, torch.device("cpu"), "probe", (1,), lambda: 1 / 0) is ws
+        assert not copy.deepcopy(net).__dict__.get("_workspaces")
+
+
 def test_tie_survives_deepcopy_and_assign():
     """FC1's two branch parameters stay row slices of the storage the fast path multiplies by
     after copy.deepcopy and load_state_dict(assign=True)"""
