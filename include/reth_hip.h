@@ -874,6 +874,54 @@ int rth_cartpole_reset(const rth_mlp_actor_args *args, void *stream);
 int rth_mlp_actor_step(rth_nstep *h, const rth_mlp_actor_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Device-resident classic-control actors on the MLP kernels (csrc/env_actor.hpp): the one launch
+ * per env step of rth_mlp_actor_step, generic over a family of gym 0.17.3 classic-control
+ * environments, each at its own network shape (H = 128):
+ *   RTH_ENV_CARTPOLE     CartPole-v0/v1   D = 4, A = 2, reward 1
+ *   RTH_ENV_ACROBOT      Acrobot-v1       D = 6, A = 3, reward -1 (0 on the terminal step)
+ *   RTH_ENV_MOUNTAINCAR  MountainCar-v0   D = 2, A = 3, reward -1
+ * The dynamics are those of reth_amd/envs.py's host classes in fp64, in their operation order.
+ * rth_mlp_actor_args' fields keep their meaning; what differs is noted.  With RTH_ENV_CARTPOLE
+ * the two entry points compute what rth_cartpole_reset / rth_mlp_actor_step compute, bit for bit.
+ * ---------------------------------------------------------------------------------- */
+enum { RTH_ENV_CARTPOLE = 0, RTH_ENV_ACROBOT = 1, RTH_ENV_MOUNTAINCAR = 2 };
+typedef struct rth_env_actor_args {
+  const float *const *params;
+  int64_t env;                /* RTH_ENV_* */
+  int64_t D, H, A;            /* must be the env's */
+  double *state;              /* [N, 4] fp64 env state; columns the env does not use stay 0 */
+  int32_t *ep_steps;
+  int64_t *t_dev;
+  int64_t *stats;             /* [N, 3] finished episodes, sum of their lengths, last length */
+  double *ret_stats;          /* [N, 3] fp64: running return, sum of finished returns, last finished return */
+  float *obs_ring;            /* [N * ring + 1, LD] f32, LD = D rounded up to 4 (pad floats 0), 16-byte aligned;
+                                 last row: zero sink */
+  int64_t *cur_slot;
+  const double *eps;
+  const int64_t *action_in;   /* nullable */
+  int64_t *action;
+  float *reward, *done;
+  int64_t *s0_h, *s1_h;
+  int32_t *emit;
+  int64_t *row_s0, *row_a, *row_s1;
+  float *row_r, *row_done;
+  float *row_obs0, *row_obs1; /* out [N, D] dense: the emitted row's observations by value (16-byte aligned) */
+  float *q_out;               /* out [N, A] nullable */
+  uint64_t seed;
+  int64_t N;
+  int32_t ring;               /* slots per env: >= 4 and >= 2 (n_step + 2) */
+  int32_t max_episode_steps;  /* TimeLimit: CartPole-v0 / MountainCar-v0 200, CartPole-v1 / Acrobot-v1 500 */
+} rth_env_actor_args;
+/* env.reset() of every env: states from Philox(seed, env, t = 0) on the env's stream (mapping:
+ * csrc/env_actor.hpp), ep_steps / t_dev / stats / ret_stats = 0, the observation into ring slot 1,
+ * cur_slot = 1.  Arguments are checked before anything is launched (RTH_ERR_INVALID, rth_last_error). */
+int rth_env_reset(const rth_env_actor_args *args, void *stream);
+/* One env step of all N actors, one launch: rth_mlp_actor_step with the env's dynamics, reward,
+ * terminal rule and observation map, and the return statistics.  args->N must equal the adder's.
+ * Arguments are checked before anything is launched. */
+int rth_env_actor_step(rth_nstep *h, const rth_env_actor_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Learner -> actor weights: a device-resident latest-wins slot with a device version.
  * Replaces perwez's PUB/SUB CONFLATE weights channel (perwez/perwez/client/socket.py:19-122,
  * 302-328: SendSocket.send / RecvSocket.recv / RecvSocket.empty) as used by

@@ -99,6 +99,20 @@ class MlpActorArgs(ctypes.Structure):
                 ("seed", c_u64), ("N", c_i64), ("ring", c_i32), ("max_episode_steps", c_i32)]
 
 
+ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR = 0, 1, 2  # RTH_ENV_*
+
+
+class EnvActorArgs(ctypes.Structure):
+    """rth_env_actor_args"""
+    _fields_ = [("params", ctypes.POINTER(c_vp)), ("env", c_i64), ("D", c_i64), ("H", c_i64), ("A", c_i64),
+                ("state", c_vp), ("ep_steps", c_vp), ("t_dev", c_vp), ("stats", c_vp), ("ret_stats", c_vp),
+                ("obs_ring", c_vp), ("cur_slot", c_vp), ("eps", c_vp), ("action_in", c_vp), ("action", c_vp),
+                ("reward", c_vp), ("done", c_vp), ("s0_h", c_vp), ("s1_h", c_vp), ("emit", c_vp), ("row_s0", c_vp),
+                ("row_a", c_vp), ("row_s1", c_vp), ("row_r", c_vp), ("row_done", c_vp), ("row_obs0", c_vp),
+                ("row_obs1", c_vp), ("q_out", c_vp), ("seed", c_u64), ("N", c_i64), ("ring", c_i32),
+                ("max_episode_steps", c_i32)]
+
+
 # name -> (restype, argtypes); must match include/reth_hip.h exactly
 SIGNATURES = {
     "rth_last_error": (ctypes.c_char_p, []),
@@ -254,6 +268,9 @@ SIGNATURES = {
     # the CartPole actors on the MLP kernels (mlp_actor.hpp)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),
     "rth_mlp_actor_step": (c_i32, [c_vp, ctypes.POINTER(MlpActorArgs), c_vp]),
+    # the classic-control family on the same step (env_actor.hpp)
+    "rth_env_reset": (c_i32, [ctypes.POINTER(EnvActorArgs), c_vp]),
+    "rth_env_actor_step": (c_i32, [c_vp, ctypes.POINTER(EnvActorArgs), c_vp]),
     # learner -> actor weights slot (perwez PUB/SUB CONFLATE)
     "rth_weights_create": (c_i32, [c_i64, c_i32, ctypes.POINTER(c_vp)]),
     "rth_weights_destroy": (c_i32, [c_vp]),

@@ -5,6 +5,9 @@ examples/dqn/config.yaml names CartPole-v0; gym 0.17.3 is its pinned dependency)
 integration of the cart-pole ODE, terminal when |x| > 2.4 or |theta| > 12 degrees, reward
 1 per step, TimeLimit 200 (v0) / 500 (v1).  Trajectories are not a parity claim (SURVEY
 §8c: env dynamics are outside the path); the spaces and the step/reset contract are.
+Acrobot (Acrobot-v1, TimeLimit 500) and MountainCar (MountainCar-v0, TimeLimit 200) restate
+gym 0.17.3's definitions the same way; the three are the host definitions of the device envs
+(csrc/env_actor.hpp), which follow them operation for operation.
 
 Atari names (`<Game>NoFrameskip-v4`, the apex configs) give `SyntheticAtari`: the spaces of
 the reference's wrapped env (env/util.py:281-297, wrap_deepmind + 4-frame stack: uint8
@@ -62,6 +65,113 @@ class CartPole:
         done = bool(x < -self.x_threshold or x > self.x_threshold or theta < -self.theta_threshold
                     or theta > self.theta_threshold or self._t >= self.max_episode_steps)
         return np.array(self.state), 1.0, done, {}
+
+
+class Acrobot:
+    """gym 0.17.3's Acrobot-v1 (classic_control/acrobot.py, the "book" dynamics, no torque noise):
+    state (theta1, theta2, omega1, omega2), torque a - 1, one classical RK4 step of dt, the angles
+    wrapped into [-pi, pi] by repeated +-2 pi, the velocities clamped to +-4 pi / +-9 pi; terminal
+    when -cos theta1 - cos(theta1 + theta2) > 1, reward 0 on a terminal step and -1 otherwise;
+    observation (cos theta1, sin theta1, cos theta2, sin theta2, omega1, omega2).  Plain floats,
+    every operation rounded once, left to right as written: the definition the device env
+    (csrc/env_actor.hpp) follows operation for operation."""
+    m1, m2, l1, lc1, lc2, I1, I2, g, dt = 1.0, 1.0, 1.0, 0.5, 0.5, 1.0, 1.0, 9.8, 0.2
+    max_vel_1, max_vel_2 = 4 * math.pi, 9 * math.pi
+
+    def __init__(self, max_episode_steps=500, seed=None):
+        high = np.array([1.0, 1.0, 1.0, 1.0, self.max_vel_1, self.max_vel_2], dtype=np.float32)
+        self.observation_space = Box(-high, high, (6,), np.float32)
+        self.action_space = Discrete(3)
+        self.max_episode_steps = max_episode_steps
+        self.np_random = np.random.RandomState(seed)
+        self.state = None
+        self._t = 0
+
+    def _obs(self):
+        t1, t2, w1, w2 = (float(v) for v in self.state)
+        return np.array([math.cos(t1), math.sin(t1), math.cos(t2), math.sin(t2), w1, w2])
+
+    def reset(self):
+        self.state = self.np_random.uniform(low=-0.1, high=0.1, size=(4,))
+        self._t = 0
+        return self._obs()
+
+    def _dsdt(self, y, tau):
+        m1, m2, l1, lc1, lc2, I1, I2, g = self.m1, self.m2, self.l1, self.lc1, self.lc2, self.I1, self.I2, self.g
+        t1, t2, w1, w2 = y
+        c2, s2 = math.cos(t2), math.sin(t2)
+        d1 = m1 * lc1 * lc1 + m2 * (l1 * l1 + lc2 * lc2 + 2.0 * l1 * lc2 * c2) + I1 + I2
+        d2 = m2 * (lc2 * lc2 + l1 * lc2 * c2) + I2
+        phi2 = m2 * lc2 * g * math.cos(t1 + t2 - math.pi / 2.0)
+        phi1 = (-m2 * l1 * lc2 * (w2 * w2) * s2 - 2.0 * m2 * l1 * lc2 * w2 * w1 * s2
+                + (m1 * lc1 + m2 * l1) * g * math.cos(t1 - math.pi / 2.0) + phi2)
+        a2 = (tau + d2 / d1 * phi1 - m2 * l1 * lc2 * (w1 * w1) * s2 - phi2) / (m2 * lc2 * lc2 + I2 - d2 * d2 / d1)
+        a1 = -(d2 * a2 + phi1) / d1
+        return (w1, w2, a1, a2)
+
+    def step(self, action):
+        assert action in (0, 1, 2), action
+        y0 = tuple(float(v) for v in self.state)
+        tau = float(int(action) - 1)
+        dt, dt2, dt6 = self.dt, self.dt / 2.0, self.dt / 6.0
+        k1 = self._dsdt(y0, tau)
+        k2 = self._dsdt(tuple(y0[j] + dt2 * k1[j] for j in range(4)), tau)
+        k3 = self._dsdt(tuple(y0[j] + dt2 * k2[j] for j in range(4)), tau)
+        k4 = self._dsdt(tuple(y0[j] + dt * k3[j] for j in range(4)), tau)
+        t1, t2, w1, w2 = (y0[j] + dt6 * (k1[j] + 2.0 * k2[j] + 2.0 * k3[j] + k4[j]) for j in range(4))
+        two_pi = 2.0 * math.pi
+        while t1 > math.pi:
+            t1 = t1 - two_pi
+        while t1 < -math.pi:
+            t1 = t1 + two_pi
+        while t2 > math.pi:
+            t2 = t2 - two_pi
+        while t2 < -math.pi:
+            t2 = t2 + two_pi
+        w1 = -self.max_vel_1 if w1 < -self.max_vel_1 else (self.max_vel_1 if w1 > self.max_vel_1 else w1)
+        w2 = -self.max_vel_2 if w2 < -self.max_vel_2 else (self.max_vel_2 if w2 > self.max_vel_2 else w2)
+        self.state = (t1, t2, w1, w2)
+        self._t += 1
+        terminal = bool(-math.cos(t1) - math.cos(t2 + t1) > 1.0)
+        return self._obs(), (0.0 if terminal else -1.0), bool(terminal or self._t >= self.max_episode_steps), {}
+
+
+class MountainCar:
+    """gym 0.17.3's MountainCar-v0 (classic_control/mountain_car.py): state (position, velocity),
+    force (a - 1) * 0.001 against gravity 0.0025 cos(3 p), |v| <= 0.07, p in [-1.2, 0.6], the left
+    wall inelastic; terminal when p >= 0.5 and v >= 0, reward -1 every step; the observation is
+    the state.  The definition the device env (csrc/env_actor.hpp) follows."""
+    min_position, max_position, max_speed, goal_position, goal_velocity = -1.2, 0.6, 0.07, 0.5, 0.0
+    force, gravity = 0.001, 0.0025
+
+    def __init__(self, max_episode_steps=200, seed=None):
+        low = np.array([self.min_position, -self.max_speed], dtype=np.float32)
+        high = np.array([self.max_position, self.max_speed], dtype=np.float32)
+        self.observation_space = Box(low, high, (2,), np.float32)
+        self.action_space = Discrete(3)
+        self.max_episode_steps = max_episode_steps
+        self.np_random = np.random.RandomState(seed)
+        self.state = None
+        self._t = 0
+
+    def reset(self):
+        self.state = np.array([self.np_random.uniform(low=-0.6, high=-0.4), 0.0])
+        self._t = 0
+        return np.array(self.state)
+
+    def step(self, action):
+        assert action in (0, 1, 2), action
+        p, v = (float(x) for x in self.state)
+        v = v + (float(int(action) - 1) * self.force + math.cos(3.0 * p) * (-self.gravity))
+        v = -self.max_speed if v < -self.max_speed else (self.max_speed if v > self.max_speed else v)
+        p = p + v
+        p = self.min_position if p < self.min_position else (self.max_position if p > self.max_position else p)
+        if p == self.min_position and v < 0.0:
+            v = 0.0
+        self.state = (p, v)
+        self._t += 1
+        terminal = bool(p >= self.goal_position and v >= self.goal_velocity)
+        return np.array(self.state), -1.0, bool(terminal or self._t >= self.max_episode_steps), {}
 
 
 # ALE minimal action-set sizes of the games the configs name (and a few common ones)
@@ -188,10 +298,14 @@ def make(name, **kwargs):
         return CartPole(200, **kwargs)
     if name == "CartPole-v1":
         return CartPole(500, **kwargs)
+    if name == "Acrobot-v1":
+        return Acrobot(500, **kwargs)
+    if name == "MountainCar-v0":
+        return MountainCar(200, **kwargs)
     name = name.strip()
     if name.endswith("NoFrameskip-v4") and name[: -len("NoFrameskip-v4")] in ATARI_ACTIONS:
         return SyntheticAtari(name[: -len("NoFrameskip-v4")], **kwargs)
-    raise NotImplementedError(f"environment {name!r}: gym/ALE are not part of this build (CartPole-v0/v1 are "
-                              "restated, Paddle-v0 is the device game's host form, Atari names get SyntheticAtari; "
+    raise NotImplementedError(f"environment {name!r}: gym/ALE are not part of this build (CartPole-v0/v1, Acrobot-v1 "
+                              "and MountainCar-v0 are restated, Paddle-v0 is the device game's host form, Atari names get SyntheticAtari; "
                               "Atari observations: "
                               "reth_amd.atari.AtariPreprocessor)")

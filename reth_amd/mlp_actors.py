@@ -11,6 +11,9 @@ DQNSolver.calc_loss_device and HbmReplay.append consume them as dense tensors.  
 synchronisation anywhere; every per-step scalar is device-resident, so a captured step replays.
 
 The counterpart of actors.VecActors (conv observations) for 1-D observations.
+
+VecMlpActors is the same actor set for the classic-control family of csrc/env_actor.hpp
+(rth_env_actor_step: CartPole, Acrobot-v1, MountainCar-v0), each env at its own network shape.
 """
 import numpy as np
 import torch
@@ -23,6 +26,11 @@ OBS_DIM, NUM_ACTIONS = 4, 2
 
 
 class VecCartPoleActors:
+    name = "CartPole"
+    obs_dim, num_actions = OBS_DIM, NUM_ACTIONS
+    ld = 4  # the ring's row stride in floats
+    _reset_fn, _step_fn = "rth_cartpole_reset", "rth_mlp_actor_step"
+
     def __init__(self, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=200, nstep_mode=0,
                  device=None):
         self.N = int(n_actors)
@@ -37,13 +45,14 @@ class VecCartPoleActors:
         while ring < 2 * (self.n_step + 3):  # an emitted row's observations are at most n + 1 steps old, 2 slots a step
             ring *= 2
         self.ring = ring
-        N = self.N
+        N, D = self.N, self.obs_dim
         z = self._alloc
         self.state = z((N, 4), torch.float64)
         self.ep_steps = z((N,), torch.int32)
         self.t_dev = z((N,), torch.int64)          # env steps taken, one equal copy per env (the Philox counter)
         self.stats = z((N, 3), torch.int64)        # finished episodes, sum of their lengths, last length
-        self.obs_ring = z((N * ring + 1, OBS_DIM), torch.float32)  # zero-filled once; last row: the sink
+        self._alloc_more()
+        self.obs_ring = z((N * ring + 1, self.ld), torch.float32)  # zero-filled once; last row: the sink
         self.cur_slot = z((N,), torch.int64)
         e = apex_epsilons(N) if eps is None else np.array(np.broadcast_to(np.asarray(eps, np.float64), (N,)))
         # float64, read by every step: overwrite in place (eps.copy_ / eps.fill_) to follow a schedule
@@ -54,7 +63,7 @@ class VecCartPoleActors:
         self.emit = z((N,), torch.int32)
         self.row_s0, self.row_a, self.row_s1 = z((N,), torch.int64), z((N,), torch.int64), z((N,), torch.int64)
         self.row_r, self.row_done = z((N,), torch.float32), z((N,), torch.float32)
-        self.row_obs0, self.row_obs1 = z((N, OBS_DIM), torch.float32), z((N, OBS_DIM), torch.float32)
+        self.row_obs0, self.row_obs1 = z((N, D), torch.float32), z((N, D), torch.float32)
         self.q_out = None  # want_q(): the acting Q rows [N, A] (tests)
         self._base = torch.arange(N, device=self.device, dtype=torch.int64) * ring
         h = _lib.c_vp()
@@ -64,12 +73,15 @@ class VecCartPoleActors:
         self._nstep = h.value
         self._params_key = self._params_arr = None
         self.pushes = 0    # env steps issued (host mirror of t_dev)
-        self.launches = 0  # rth_mlp_actor_step calls: one launch each
+        self.launches = 0  # actor-step calls: one launch each
         self.reset()
 
     def _alloc(self, shape, dtype):
         """a zero-filled device buffer (tests override it to surround every buffer with guards)"""
         return torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def _alloc_more(self):
+        """a subclass's further state buffers"""
 
     def __del__(self):
         if getattr(self, "_nstep", None):
@@ -84,8 +96,10 @@ class VecCartPoleActors:
         ps = q_network._params6()
         key = tuple(p.data_ptr() for p in ps)
         if key != self._params_key:
-            if not q_network.hip_supported() or q_network.dims() != (OBS_DIM, 128, NUM_ACTIONS):
-                raise ValueError(f"the CartPole actors run MLP_DQNNetwork((4,), 2) on the GPU, got dims {q_network.dims()}")
+            want = (self.obs_dim, 128, self.num_actions)
+            if not q_network.hip_supported() or q_network.dims() != want:
+                raise ValueError(f"the {self.name} actors run MLP_DQNNetwork(({want[0]},), {want[2]}) on the GPU, got "
+                                 f"dims {q_network.dims()}")
             self._params_arr = (_lib.c_vp * 6)(*key)
             self._params_key = key
         return self._params_arr
@@ -105,13 +119,13 @@ class VecCartPoleActors:
         step counters and episode statistics"""
         s = stream_ptr()
         args = self._args()
-        call("rth_cartpole_reset", _lib.ctypes.byref(args), s)
+        call(self._reset_fn, _lib.ctypes.byref(args), s)
         call("rth_nstep_reset", self._nstep, s)
         self.pushes = 0
 
     def want_q(self, on=True):
         """have every step also write its acting Q rows to q_out [N, A] (tests)"""
-        self.q_out = self._alloc((self.N, NUM_ACTIONS), torch.float32) if on else None
+        self.q_out = self._alloc((self.N, self.num_actions), torch.float32) if on else None
         return self.q_out
 
     @torch.no_grad()
@@ -143,7 +157,7 @@ class VecCartPoleActors:
                     and action_in.numel() == self.N and action_in.is_contiguous()):
                 raise ValueError("action_in: a contiguous int64 device tensor [N]")
         args = self._args(self._params(q_network), action_in)
-        call("rth_mlp_actor_step", self._nstep, _lib.ctypes.byref(args), stream_ptr())
+        call(self._step_fn, self._nstep, _lib.ctypes.byref(args), stream_ptr())
         self.launches += 1
         self.pushes += 1
         return self.warm
@@ -166,10 +180,87 @@ class VecCartPoleActors:
         return self.stats[:, 0], self.stats[:, 1], self.stats[:, 2]
 
     @staticmethod
-    def columns():
+    def columns(obs_dim=OBS_DIM):
         """replay columns of the rows [s0, a, r, s1, done], cast f4 / i8 / f4 / f4 / f4 as
         test/apex-dqn/worker.py:47-51 casts them"""
         from .replay import Column
 
-        return [Column((OBS_DIM,), torch.float32), Column((), torch.int64), Column((), torch.float32),
-                Column((OBS_DIM,), torch.float32), Column((), torch.float32)]
+        return [Column((obs_dim,), torch.float32), Column((), torch.int64), Column((), torch.float32),
+                Column((obs_dim,), torch.float32), Column((), torch.float32)]
+
+
+# env name -> (RTH_ENV_* id, obs_dim, num_actions, TimeLimit) of the classic-control family (csrc/env_actor.hpp)
+ENVS = {"CartPole-v0": (_lib.ENV_CARTPOLE, 4, 2, 200), "CartPole-v1": (_lib.ENV_CARTPOLE, 4, 2, 500),
+        "Acrobot-v1": (_lib.ENV_ACROBOT, 6, 3, 500), "MountainCar-v0": (_lib.ENV_MOUNTAINCAR, 2, 3, 200)}
+
+
+class VecMlpActors(VecCartPoleActors):
+    """VecCartPoleActors for the classic-control family: N envs of `env` (a key of ENVS: the host
+    classes of envs.py, fp64) stepped by one launch of rth_env_actor_step at the env's network
+    shape (obs_dim, 128, num_actions), with the env's reward, terminal rule and observation map.
+    The ring's rows are obs_dim rounded up to 4 floats (the pad stays 0); rows() are dense
+    [N, obs_dim].  Adds fp64 return statistics (return_stats).  max_episode_steps defaults to the
+    env's TimeLimit.  With a CartPole name it computes what VecCartPoleActors computes, bit for
+    bit, through the generic entry point."""
+    _reset_fn, _step_fn = "rth_env_reset", "rth_env_actor_step"
+
+    def __init__(self, env, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=None, nstep_mode=0,
+                 device=None):
+        if env not in ENVS:
+            raise ValueError(f"VecMlpActors: unknown env {env!r} (device envs: {', '.join(ENVS)})")
+        self.env = self.name = env
+        self.env_id, self.obs_dim, self.num_actions, limit = ENVS[env]
+        self.ld = (self.obs_dim + 3) // 4 * 4
+        super().__init__(n_actors, n_step, gamma, eps, seed, limit if max_episode_steps is None else max_episode_steps,
+                         nstep_mode, device)
+
+    def _alloc_more(self):
+        # running return, sum of the finished episodes' returns, last finished return
+        self.ret_stats = self._alloc((self.N, 3), torch.float64)
+
+    def _args(self, params=None, action_in=None):
+        return _lib.EnvActorArgs(params, self.env_id, self.obs_dim, 128, self.num_actions, ptr(self.state),
+                                 ptr(self.ep_steps), ptr(self.t_dev), ptr(self.stats), ptr(self.ret_stats),
+                                 ptr(self.obs_ring), ptr(self.cur_slot), ptr(self.eps), ptr(action_in),
+                                 ptr(self.action), ptr(self.reward), ptr(self.done), ptr(self.s0_h), ptr(self.s1_h),
+                                 ptr(self.emit), ptr(self.row_s0), ptr(self.row_a), ptr(self.row_s1), ptr(self.row_r),
+                                 ptr(self.row_done), ptr(self.row_obs0), ptr(self.row_obs1), ptr(self.q_out),
+                                 self.seed, self.N, self.ring, self.max_episode_steps)
+
+    def observe(self, state):
+        """the env's f32 observation [N, ld] (pad 0) of fp64 states [N, 4], computed by torch"""
+        obs = torch.zeros((state.shape[0], self.ld), dtype=torch.float32, device=state.device)
+        if self.env_id == _lib.ENV_ACROBOT:
+            t = state[:, :2]
+            obs[:, 0:4:2], obs[:, 1:4:2] = torch.cos(t).float(), torch.sin(t).float()
+            obs[:, 4:6] = state[:, 2:4].float()
+        else:
+            obs[:, :self.obs_dim] = state[:, :self.obs_dim].float()
+        return obs
+
+    @torch.no_grad()
+    def set_state(self, states, steps=None):
+        """inject env states [N, 4] (float64; [N, k] fills the first k columns) and, optionally, the
+        running episodes' step counts [N]; the observations the envs act on next become those of
+        the states (tests)"""
+        st = torch.as_tensor(np.asarray(states, np.float64) if not torch.is_tensor(states) else states)
+        st = st.to(self.device, torch.float64).reshape(self.N, -1)
+        self.state.zero_()
+        self.state[:, :st.shape[1]] = st
+        if steps is not None:
+            sp = torch.as_tensor(np.asarray(steps) if not torch.is_tensor(steps) else steps)
+            self.ep_steps.copy_(sp.to(self.device, torch.int32).reshape(self.N))
+        self.obs_ring[self._base + self.cur_slot] = self.observe(self.state)
+
+    def current_obs(self):
+        """the observations [N, obs_dim] the envs act on next (a dense copy)"""
+        return self.obs_ring[self._base + self.cur_slot][:, :self.obs_dim].contiguous()
+
+    def return_stats(self):
+        """per-env device statistics (float64 [N] each): the running episode's return, the sum of
+        the finished episodes' returns, the last finished return"""
+        return self.ret_stats[:, 0], self.ret_stats[:, 1], self.ret_stats[:, 2]
+
+    def columns(self):
+        """replay columns of the rows [s0, a, r, s1, done] at this env's obs_dim"""
+        return VecCartPoleActors.columns(self.obs_dim)

@@ -1,11 +1,12 @@
-"""Ape-X DQN for 1-D observations on one GPU and one stream: the device CartPole loop.
+"""Ape-X DQN for 1-D observations on one GPU and one stream: the device classic-control loop
+(CartPole by default; MlpApexConfig.env names another env of mlp_actors.ENVS).
 
 The counterpart of apex.ApexDQN (conv observations) on the fused MLP kernels.  Reference wiring:
 reth/examples/dqn/run.py (worker.step_batch -> solver.calc_loss -> buffer.append_batch ->
 buffer.sample -> trainer.step -> buffer.update_priorities) with the actor side of
 presets/worker.py:128-155.  One iteration, entirely in HBM and without host synchronisation:
 
-    1. VecCartPoleActors.step           one launch: act, env, reset, n-step push (N env steps)
+    1. the actors' step                 one launch: act, env, reset, n-step push (N env steps)
     2. solver.calc_loss_device(rows)    the emitted rows' |td|: their priorities
     3. HbmReplay.append                 PER insert of the N rows
     4. once sample_start rows are stored:
@@ -27,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import model
-from .mlp_actors import NUM_ACTIONS, OBS_DIM, VecCartPoleActors
+from .mlp_actors import ENVS, NUM_ACTIONS, OBS_DIM, VecCartPoleActors, VecMlpActors
 from .replay import HbmReplay
 from .schedule import Interval
 from .solver import Box, DQNSolver, Discrete
@@ -48,10 +49,11 @@ class MlpApexConfig:
     double_q: bool = True
     update_target_interval: int = 200
     sample_start: int = 1000           # rows stored before the first update
-    max_episode_steps: int = 200       # CartPole-v0 (500: v1)
+    max_episode_steps: Optional[int] = None  # None: the env's TimeLimit (CartPole-v0 200, v1 500, ...)
     nstep_mode: int = 0
     eps: Optional[object] = None       # None: apex_epsilons(n_actors)
     seed: int = 0
+    env: str = "CartPole-v0"           # a key of mlp_actors.ENVS: the reference's env.name (examples/dqn/config.yaml)
 
 
 class MlpApexDQN:
@@ -62,10 +64,17 @@ class MlpApexDQN:
                                f"constructing it (MLP_IMPL is {model.MLP_IMPL!r}); there is no torch fallback")
         if cfg.sample_start < 1 or cfg.batch_size < 1:
             raise ValueError("sample_start and batch_size must be >= 1")
+        if cfg.env not in ENVS:
+            raise ValueError(f"MlpApexConfig.env {cfg.env!r}: the device envs are {', '.join(ENVS)}")
         self.cfg = cfg
         self.device = torch.device(device if device is not None else "cuda")
+        _, obs_dim, num_actions, limit = ENVS[cfg.env]
+        self.max_episode_steps = int(limit if cfg.max_episode_steps is None else cfg.max_episode_steps)
+        # CartPole keeps the actors it was brought up on (rth_mlp_actor_step); the other envs run
+        # the generic step (rth_env_actor_step)
+        self._cartpole = (obs_dim, num_actions) == (OBS_DIM, NUM_ACTIONS)
         torch.manual_seed(cfg.seed)
-        self.solver = DQNSolver(Box(-1, 1, (OBS_DIM,)), Discrete(NUM_ACTIONS), gamma=cfg.gamma,
+        self.solver = DQNSolver(Box(-1, 1, (obs_dim,)), Discrete(num_actions), gamma=cfg.gamma,
                                 clip_value=cfg.clip_value, double_q=cfg.double_q, dueling=True,
                                 learning_rate=cfg.learning_rate, adam_epsilon=cfg.adam_epsilon,
                                 update_target_interval=cfg.update_target_interval, device=self.device,
@@ -75,10 +84,9 @@ class MlpApexDQN:
         # the target sync: host Interval outside the (possibly captured) iteration
         self.solver.auto_target_update = False
         self._target_interval = Interval(self.solver.update_target, cfg.update_target_interval)
-        self.actors = VecCartPoleActors(cfg.n_actors, cfg.n_step, cfg.gamma, eps=cfg.eps, seed=cfg.seed,
-                                        max_episode_steps=cfg.max_episode_steps, nstep_mode=cfg.nstep_mode,
-                                        device=self.device)
-        self.replay = HbmReplay(cfg.capacity, VecCartPoleActors.columns(), cfg.alpha, cfg.beta, self.device,
+        self.actors = self._make_actors(cfg.n_actors, cfg.n_step, eps=cfg.eps, seed=cfg.seed,
+                                        nstep_mode=cfg.nstep_mode)
+        self.replay = HbmReplay(cfg.capacity, self.actors.columns(), cfg.alpha, cfg.beta, self.device,
                                 seed=cfg.seed + 7919)
         self.batch, self.idx, self.isw = self.replay.new_batch(cfg.batch_size)
         self.iterations = 0
@@ -88,6 +96,13 @@ class MlpApexDQN:
         self.solver_calls = 0  # calc_loss_device + update_device calls issued (solver.mlp_hip_launches)
         self._graph = None
         self._graph_keep = None
+
+    def _make_actors(self, n, n_step, **kw):
+        if self._cartpole:
+            return VecCartPoleActors(n, n_step, self.cfg.gamma, max_episode_steps=self.max_episode_steps,
+                                     device=self.device, **kw)
+        return VecMlpActors(self.cfg.env, n, n_step, self.cfg.gamma, max_episode_steps=self.max_episode_steps,
+                            device=self.device, **kw)
 
     # ------------------------------------------------------------------ one iteration
     def _learning(self):
@@ -169,18 +184,26 @@ class MlpApexDQN:
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()
-    def greedy_eval(self, n_envs=256, seed=12345, max_steps=None):
-        """mean length of the first episode of each of n_envs greedy (ε = 0) envs of a separate
+    def greedy_eval(self, n_envs=256, seed=12345, max_steps=None, metric="length"):
+        """mean length (metric="length") or mean return (metric="return", from the fp64 return
+        statistics) of the first episode of each of n_envs greedy (ε = 0) envs of a separate
         actor set under the current online network, from the device statistics.  Every env finishes
         its first episode within max_episode_steps steps (TimeLimit); taking each env's first
         episode -- not every episode finished in the window -- keeps short episodes from counting
         more often than long ones.  One host read, at the end."""
-        ev = VecCartPoleActors(n_envs, 1, self.cfg.gamma, eps=0.0, seed=seed,
-                               max_episode_steps=self.cfg.max_episode_steps, device=self.device)
-        first = torch.zeros(ev.N, dtype=torch.int64, device=self.device)
+        if metric not in ("length", "return"):
+            raise ValueError('greedy_eval: metric is "length" or "return"')
+        if metric == "return" and self._cartpole:  # reward 1 a step: the return is the length
+            metric = "length"
+        ev = self._make_actors(n_envs, 1, eps=0.0, seed=seed)
         episodes, _, last = ev.episode_stats()
-        for _ in range(self.cfg.max_episode_steps if max_steps is None else int(max_steps)):
+        if metric == "return":
+            last = ev.return_stats()[2]
+        first = torch.zeros(ev.N, dtype=last.dtype, device=self.device)
+        seen = torch.zeros(ev.N, dtype=torch.bool, device=self.device)
+        for _ in range(self.max_episode_steps if max_steps is None else int(max_steps)):
             ev.step(self.solver.q_network)
-            first = torch.where((first == 0) & (episodes > 0), last, first)
-        done = first > 0
-        return float((first.sum() / done.sum().clamp(min=1)).item())
+            fresh = ~seen & (episodes > 0)
+            first = torch.where(fresh, last, first)
+            seen |= fresh
+        return float((first.sum() / seen.sum().clamp(min=1)).item())
