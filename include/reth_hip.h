@@ -922,6 +922,50 @@ int rth_env_reset(const rth_env_actor_args *args, void *stream);
 int rth_env_actor_step(rth_nstep *h, const rth_env_actor_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * DDPG's actor and critic (ddpg_model.py:76-122) as fused fp32 kernels (ddpg.hpp):
+ *   actor   fc1 (D -> H1), ReLU, fc2 (H1 -> H2), ReLU, fc3 (H2 -> Ad), tanh
+ *   critic  fc1 (D -> H1), ReLU, fc2 (H1 + Ad -> H2) on cat(relu(fc1(s)), a), ReLU, fc3 (H2 -> 1)
+ * A network is a HOST array of six device pointers in torch layout, read in place: {fc1.weight,
+ * fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias}; gradients have the same order and shapes
+ * (every element written, nothing accumulated).  Built for D in 1..64, Ad in 1..8, H1 and H2
+ * multiples of 4 in 4..512, any n, B >= 1; other shapes return RTH_ERR_INVALID and launch nothing.
+ * Every product is one fp32 fmaf and a dot product has one fixed summation order, so a row's
+ * action or Q does not depend on n, on the row's position or on the entry point; the gradients
+ * sum over the batch in a fixed order (no atomics).  tanh is evaluated in fp64 and rounded once.
+ * Inputs are fp32 matrices with unit column stride and the given row strides (in floats).  All
+ * launches go to `stream`, without host synchronisation or allocation.
+ * ---------------------------------------------------------------------------------- */
+int rth_ddpg_supported(int64_t D, int64_t Ad, int64_t H1, int64_t H2); /* 1 where built, else 0 */
+/* bytes for rth_ddpg_critic_grads / rth_ddpg_actor_grads (one size serves both); < 0: error */
+int64_t rth_ddpg_workspace(int64_t B, int64_t D, int64_t Ad, int64_t H1, int64_t H2);
+/* act_out[n, Ad] = actor(x[n, D]), dense rows.  One launch (ddpg_solver.py:112-118). */
+int rth_ddpg_act(const float *const *actor, const float *x_dev, int64_t ldx, int64_t n, int64_t D, int64_t Ad,
+                 int64_t H1, int64_t H2, float *act_out_dev, void *stream);
+/* ddpg_solver.py:79-94: a1 = actor_target(s1), y = r + ((1 - done) * gamma) * critic_target(s1, a1),
+ * td = critic(s0, a) - y, loss = mean(td^2 * isw) (isw fp32, nullable) and the backward into the
+ * critic's grads[6].  grads == NULL: no backward (calc_loss).  td_abs_dev [B] = |td|, loss_dev [1]
+ * nullable.  At most two launches. */
+int rth_ddpg_critic_grads(const float *const *critic, const float *const *actor_target,
+                          const float *const *critic_target, const float *s0_dev, int64_t lds0, const float *a_dev,
+                          int64_t lda, const float *r_dev, const float *done_dev, const float *s1_dev, int64_t lds1,
+                          const float *isw_dev, int64_t B, int64_t D, int64_t Ad, int64_t H1, int64_t H2, float gamma,
+                          float *const *grads, float *td_abs_dev, float *loss_dev, void *workspace_dev, void *stream);
+/* ddpg_solver.py:98-101: loss = -mean(critic(s0, actor(s0))) and its backward into the ACTOR's
+ * grads[6]: through the critic's fc3, fc2's ReLU and the action columns [H1, H1 + Ad) of its
+ * fc2.weight, through 1 - tanh^2 and the actor's three layers.  The critic is only read and no
+ * critic gradient is produced.  loss_dev [1] nullable.  Afterwards the first B * Ad floats of the
+ * workspace hold the actions actor(s0) -- rth_ddpg_act's values, bit for bit.  Two launches. */
+int rth_ddpg_actor_grads(const float *const *actor, const float *const *critic, const float *s0_dev, int64_t lds0,
+                         int64_t B, int64_t D, int64_t Ad, int64_t H1, int64_t H2, float *const *grads,
+                         float *loss_dev, void *workspace_dev, void *stream);
+/* Polyak update (algorithm/util.py:15-24) of n_tensors <= 16 tensors in one launch; target, source
+ * and numel are HOST arrays.  Per element fl(fl(t * (float)(1 - tau)) + fl(p * (float)tau)): two
+ * fp32 products and one fp32 sum, never contracted -- what torch computes for
+ * target * (1.0 - tau) + param * tau. */
+int rth_soft_update(float *const *target, const float *const *source, const int64_t *numel, int32_t n_tensors,
+                    double tau, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Learner -> actor weights: a device-resident latest-wins slot with a device version.
  * Replaces perwez's PUB/SUB CONFLATE weights channel (perwez/perwez/client/socket.py:19-122,
  * 302-328: SendSocket.send / RecvSocket.recv / RecvSocket.empty) as used by

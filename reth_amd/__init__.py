@@ -6,6 +6,7 @@ include/reth_hip.h).  Modules mirror the reference's interfaces:
     reth_amd.reth_buffer   start_per / start_server / Client / NumpyLoader / TorchCudaLoader
     reth_amd.replay        SumTree (NumbaSumTree), PERSampler, HbmReplay
     reth_amd.solver        DQNSolver (reth.algorithm.DQNSolver), td_huber_loss
+    reth_amd.ddpg          DDPGSolver (reth.algorithm.DDPGSolver), Actor, Critic
     reth_amd.trainer       Trainer (reth.presets.Trainer)
     reth_amd.actors        VecActors (the apex-dqn worker loop, vectorised on the GPU)
     reth_amd.apex          ApexDQN / ApexConfig (test/apex-dqn wiring, one process per GPU)

@@ -265,6 +265,17 @@ SIGNATURES = {
     "rth_mlp_dqn_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
                                   c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_i32, ctypes.POINTER(c_vp), c_vp,
                                   c_vp, c_vp, c_vp]),
+    # DDPG's actor and critic (ddpg.hpp)
+    "rth_ddpg_supported": (c_i32, [c_i64, c_i64, c_i64, c_i64]),
+    "rth_ddpg_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "rth_ddpg_act": (c_i32, [ctypes.POINTER(c_vp), c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "rth_ddpg_critic_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64,
+                                      c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                      c_f32, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp]),
+    "rth_ddpg_actor_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_i64, c_i64, c_i64,
+                                     c_i64, c_i64, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
+    "rth_soft_update": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_f64,
+                                c_vp]),
     # the CartPole actors on the MLP kernels (mlp_actor.hpp)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),
     "rth_mlp_actor_step": (c_i32, [c_vp, ctypes.POINTER(MlpActorArgs), c_vp]),

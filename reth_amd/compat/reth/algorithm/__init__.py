@@ -1,2 +1,3 @@
-"""`reth.algorithm` (reth/reth/algorithm/__init__.py:17-21): the DQN solver only"""
+"""`reth.algorithm` (reth/reth/algorithm/__init__.py:17-21): the DQN and DDPG solvers"""
+from reth_amd.ddpg import DDPGSolver  # noqa: F401
 from reth_amd.solver import DQNSolver, get_solver  # noqa: F401

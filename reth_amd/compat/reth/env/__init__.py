@@ -1,2 +1,2 @@
 """`reth.env` (reth/reth/env/__init__.py)"""
-from reth_amd.envs import make  # noqa: F401
+from reth_amd.envs import make_host as make  # noqa: F401

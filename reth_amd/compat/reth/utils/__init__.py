@@ -2,3 +2,4 @@
 from reth_amd.nstep import NStepAdder  # noqa: F401
 from reth_amd.schedule import Interval, Schedule  # noqa: F401
 from reth_amd.trainer import getLogger  # noqa: F401
+from reth_amd.noise import OUNoise, OUNoiseExploration  # noqa: F401

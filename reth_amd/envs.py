@@ -7,7 +7,10 @@ integration of the cart-pole ODE, terminal when |x| > 2.4 or |theta| > 12 degree
 §8c: env dynamics are outside the path); the spaces and the step/reset contract are.
 Acrobot (Acrobot-v1, TimeLimit 500) and MountainCar (MountainCar-v0, TimeLimit 200) restate
 gym 0.17.3's definitions the same way; the three are the host definitions of the device envs
-(csrc/env_actor.hpp), which follow them operation for operation.
+(csrc/env_actor.hpp), which follow them operation for operation.  Pendulum (Pendulum-v0, TimeLimit
+200) is the continuous-control environment of the reference's examples/ddpg; it has no device
+form yet and no discrete action set, so make() -- the envs of the DQN loops -- does not name it:
+make_host() does, and is what the YAML factories (presets.get_env) and `reth.env.make` call.
 
 Atari names (`<Game>NoFrameskip-v4`, the apex configs) give `SyntheticAtari`: the spaces of
 the reference's wrapped env (env/util.py:281-297, wrap_deepmind + 4-frame stack: uint8
@@ -174,6 +177,48 @@ class MountainCar:
         return np.array(self.state), -1.0, bool(terminal or self._t >= self.max_episode_steps), {}
 
 
+class Pendulum:
+    """gym 0.17.3's Pendulum-v0 (classic_control/pendulum.py): state (theta, theta_dot), the torque
+    u = clip(action[0], -2, 2); theta_dot' = theta_dot + (-3 g / (2 l) sin(theta + pi) + 3 u / (m l^2)) dt,
+    theta' = theta + theta_dot' dt, THEN theta_dot' clipped to +-8; reward -(angle_normalize(theta)^2 +
+    0.1 theta_dot^2 + 0.001 u^2) of the state before the step; observation (cos theta, sin theta,
+    theta_dot); reset uniform in [-pi, pi] x [-1, 1]; no terminal state, only the time limit."""
+    max_speed, max_torque, dt, g, m, l = 8.0, 2.0, 0.05, 10.0, 1.0, 1.0
+
+    def __init__(self, max_episode_steps=200, seed=None):
+        high = np.array([1.0, 1.0, self.max_speed], dtype=np.float32)
+        self.observation_space = Box(-high, high, (3,), np.float32)
+        self.action_space = Box(-self.max_torque, self.max_torque, (1,), np.float32)
+        self.max_episode_steps = max_episode_steps
+        self.np_random = np.random.RandomState(seed)
+        self.state = None
+        self._t = 0
+
+    def _obs(self):
+        th, thdot = (float(v) for v in self.state)
+        return np.array([math.cos(th), math.sin(th), thdot])
+
+    def reset(self):
+        high = np.array([math.pi, 1.0])
+        self.state = self.np_random.uniform(low=-high, high=high)
+        self._t = 0
+        return self._obs()
+
+    def step(self, action):
+        th, thdot = (float(v) for v in self.state)
+        u = float(np.clip(np.asarray(action, dtype=np.float64).reshape(-1)[0], -self.max_torque, self.max_torque))
+        norm = ((th + math.pi) % (2.0 * math.pi)) - math.pi
+        cost = norm ** 2 + 0.1 * thdot ** 2 + 0.001 * (u ** 2)
+        newthdot = thdot + (-3.0 * self.g / (2.0 * self.l) * math.sin(th + math.pi)
+                            + 3.0 / (self.m * self.l ** 2) * u) * self.dt
+        newth = th + newthdot * self.dt
+        newthdot = -self.max_speed if newthdot < -self.max_speed else (
+            self.max_speed if newthdot > self.max_speed else newthdot)
+        self.state = (newth, newthdot)
+        self._t += 1
+        return self._obs(), -cost, bool(self._t >= self.max_episode_steps), {}
+
+
 # ALE minimal action-set sizes of the games the configs name (and a few common ones)
 ATARI_ACTIONS = {"Pong": 6, "Breakout": 4, "BeamRider": 9, "Seaquest": 18, "SpaceInvaders": 6, "Qbert": 6,
                  "Enduro": 9, "MsPacman": 9, "Asterix": 9, "Boxing": 18, "Freeway": 3}
@@ -309,3 +354,14 @@ def make(name, **kwargs):
                               "and MountainCar-v0 are restated, Paddle-v0 is the device game's host form, Atari names get SyntheticAtari; "
                               "Atari observations: "
                               "reth_amd.atari.AtariPreprocessor)")
+
+
+HOST_ONLY = {"Pendulum-v0": lambda **kwargs: Pendulum(200, **kwargs)}
+
+
+def make_host(name, **kwargs):
+    """make(), plus the environments that exist on the host alone (continuous actions, no device
+    form): Pendulum-v0.  reth.env.make and the presets' get_env resolve names through this."""
+    if name in HOST_ONLY:
+        return HOST_ONLY[name](**kwargs)
+    return make(name, **kwargs)

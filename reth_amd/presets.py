@@ -1,7 +1,7 @@
 """reth.presets on top of the HIP path: Worker, exploration and the YAML factories.
 
-Reference: reth/reth/presets/worker.py:12-163 (Worker), reth/reth/utils/exploration.py:16-31
-(RandomExploration), reth/reth/presets/config.py:12-73 (get_env / get_solver / get_worker /
+Reference: reth/reth/presets/worker.py:12-163 (Worker), reth/reth/utils/exploration.py:16-53
+(RandomExploration; OUNoiseExploration lives in noise.py), reth/reth/presets/config.py:12-73 (get_env / get_solver / get_worker /
 get_trainer / get_replay_buffer).  The worker steps a host environment (the reference's
 examples run one gym env per process); the solver, buffers and trainer are the device
 ones (DQNSolver, reth_amd.buffer, Trainer).
@@ -15,6 +15,7 @@ import yaml
 
 from . import envs
 from .buffer import DynamicSizeBuffer, NumpyBuffer, PrioritizedBuffer
+from .noise import OUNoise, OUNoiseExploration  # noqa: F401
 from .schedule import Interval, Schedule
 from .solver import get_solver as _get_solver
 from .trainer import Trainer, getLogger
@@ -35,7 +36,9 @@ class RandomExploration:
 
 
 class Worker:
-    """worker.py:12-163 (exploration given as a number / schedule string or an object)"""
+    """worker.py:12-163 (exploration given as a number / schedule string, as the reference's dict
+    {name: random | ounoise, ...} or as an object; the ounoise form resets its noise at every
+    episode end, worker.py:49-68)"""
 
     def __init__(self, env, solver, logger=None, exploration=None, print_interval=500, device=None):
         self.env, self.solver = env, solver
@@ -50,6 +53,16 @@ class Worker:
             self.add_callback(self.print, print_interval)
         if exploration is None or hasattr(exploration, "act"):
             self.exploration = exploration
+        elif isinstance(exploration, dict):
+            name = str(exploration["name"]).lower()
+            kwargs = {k: v for k, v in exploration.items() if k != "name"}
+            if name == "random":
+                self.exploration = RandomExploration(solver, env.action_space, **kwargs)
+            elif name == "ounoise":
+                self.exploration = OUNoiseExploration(solver, env.action_space, **kwargs)
+                self.on_episode_end.append(self.exploration.reset)
+            else:
+                raise ValueError(f"Invalid exploration name {exploration['name']!r} (random, ounoise)")
         else:
             self.exploration = RandomExploration(solver, env.action_space, epsilon=exploration)
 
@@ -131,7 +144,7 @@ def _parse_input(f):
 
 
 def get_env(f, **kwargs):
-    return envs.make(**{**_parse_input(f)["env"], **kwargs})
+    return envs.make_host(**{**_parse_input(f)["env"], **kwargs})
 
 
 def get_solver(f, env=None, **kwargs):

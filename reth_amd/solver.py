@@ -422,7 +422,12 @@ class DQNSolver(Algorithm):
 
 
 def get_solver(name, **kwargs):
-    """reth/reth/algorithm/__init__.py:17-21 (only the DQN path is rebuilt)"""
-    if name != "dqn":
-        raise NotImplementedError(f"solver {name!r}: only 'dqn' is on the Ape-X hot path")
-    return DQNSolver(**kwargs)
+    """reth/reth/algorithm/__init__.py:17-21: "dqn" -> DQNSolver, "ddpg" -> DDPGSolver (ddpg.py);
+    the on-policy solvers (a2c, pg, ppo) are not rebuilt"""
+    if name == "dqn":
+        return DQNSolver(**kwargs)
+    if name == "ddpg":
+        from .ddpg import DDPGSolver
+
+        return DDPGSolver(**kwargs)
+    raise NotImplementedError(f"solver {name!r}: only 'dqn' and 'ddpg' are rebuilt")
