@@ -826,13 +826,15 @@ int rth_mlp_dqn_grads(const float *const *online, const float *const *target, co
                       void *workspace_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
- * Device-resident vectorised CartPole actors on the MLP kernels (csrc/mlp_actor.hpp): N gym
- * CartPole-v0/v1 environments stepped by one launch, without host synchronisation.  Replaces the
- * host actor loop of reth/reth/presets/worker.py:128-155 (Worker.step: act, env.step, env.reset on
- * done) and what it calls: utils/exploration.py:26-31 (RandomExploration.act),
- * algorithm/dqn/dqn_solver.py:126-131 (act = argmax Q) and utils/nstep_adder.py:11-28.
- * All pointers are device memory except `params` (a host array of six device pointers, as
- * rth_mlp_q's).  Built for D = 4, H = 128, A = 2.
+ * Device-resident vectorised CartPole actors on the MLP kernels: N gym CartPole-v0/v1
+ * environments stepped by one launch, without host synchronisation.  Replaces the host actor loop
+ * of reth/reth/presets/worker.py:128-155 (Worker.step: act, env.step, env.reset on done) and what
+ * it calls: utils/exploration.py:26-31 (RandomExploration.act), algorithm/dqn/dqn_solver.py:126-131
+ * (act = argmax Q) and utils/nstep_adder.py:11-28.  All pointers are device memory except `params`
+ * (a host array of six device pointers, as rth_mlp_q's).  Built for D = 4, H = 128, A = 2.
+ * These two entry points are adapters (csrc/mlp_actor.hpp) onto the classic-control kernels below
+ * (csrc/env_actor.hpp) with env = RTH_ENV_CARTPOLE and no return statistics: one step kernel and
+ * one reset kernel serve all four entry points.
  * ---------------------------------------------------------------------------------- */
 typedef struct rth_mlp_actor_args {
   const float *const *params; /* the acting network (rth_mlp_q layout); unused by the reset */
@@ -859,7 +861,7 @@ typedef struct rth_mlp_actor_args {
   int32_t max_episode_steps;  /* TimeLimit: 200 (v0) / 500 (v1) */
 } rth_mlp_actor_args;
 /* env.reset() of every env (worker.py:144-145): states from Philox(seed, env, t = 0) -- the counter
- * layout is documented in csrc/mlp_actor.hpp --, ep_steps / t_dev / stats = 0, the observation into
+ * layout is documented in csrc/env_actor.hpp --, ep_steps / t_dev / stats = 0, the observation into
  * ring slot 1, cur_slot = 1.  Uses state, ep_steps, t_dev, stats, obs_ring, cur_slot, seed, N, ring.
  * Arguments are checked before anything is launched (RTH_ERR_INVALID, rth_last_error). */
 int rth_cartpole_reset(const rth_mlp_actor_args *args, void *stream);
@@ -874,15 +876,18 @@ int rth_cartpole_reset(const rth_mlp_actor_args *args, void *stream);
 int rth_mlp_actor_step(rth_nstep *h, const rth_mlp_actor_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------
- * Device-resident classic-control actors on the MLP kernels (csrc/env_actor.hpp): the one launch
- * per env step of rth_mlp_actor_step, generic over a family of gym 0.17.3 classic-control
+ * Device-resident classic-control actors on the MLP kernels (csrc/env_actor.hpp): one launch per
+ * env step, one kernel templated on the env, for a family of gym 0.17.3 classic-control
  * environments, each at its own network shape (H = 128):
  *   RTH_ENV_CARTPOLE     CartPole-v0/v1   D = 4, A = 2, reward 1
  *   RTH_ENV_ACROBOT      Acrobot-v1       D = 6, A = 3, reward -1 (0 on the terminal step)
  *   RTH_ENV_MOUNTAINCAR  MountainCar-v0   D = 2, A = 3, reward -1
  * The dynamics are those of reth_amd/envs.py's host classes in fp64, in their operation order.
- * rth_mlp_actor_args' fields keep their meaning; what differs is noted.  With RTH_ENV_CARTPOLE
- * the two entry points compute what rth_cartpole_reset / rth_mlp_actor_step compute, bit for bit.
+ * rth_mlp_actor_args' fields keep their meaning; what differs is noted.  rth_cartpole_reset /
+ * rth_mlp_actor_step launch these kernels' RTH_ENV_CARTPOLE instance, so the four entry points
+ * agree bit for bit on CartPole (pinned by tests/test_classic_actors_gpu.py::
+ * test_generic_cartpole_equals_the_cartpole_actors); only these two keep ret_stats, which they
+ * require.
  * ---------------------------------------------------------------------------------- */
 enum { RTH_ENV_CARTPOLE = 0, RTH_ENV_ACROBOT = 1, RTH_ENV_MOUNTAINCAR = 2 };
 typedef struct rth_env_actor_args {
@@ -916,8 +921,8 @@ typedef struct rth_env_actor_args {
  * csrc/env_actor.hpp), ep_steps / t_dev / stats / ret_stats = 0, the observation into ring slot 1,
  * cur_slot = 1.  Arguments are checked before anything is launched (RTH_ERR_INVALID, rth_last_error). */
 int rth_env_reset(const rth_env_actor_args *args, void *stream);
-/* One env step of all N actors, one launch: rth_mlp_actor_step with the env's dynamics, reward,
- * terminal rule and observation map, and the return statistics.  args->N must equal the adder's.
+/* One env step of all N actors, one launch: the step rth_mlp_actor_step describes, with the env's
+ * dynamics, reward, terminal rule and observation map, and the return statistics.  args->N must equal the adder's.
  * Arguments are checked before anything is launched. */
 int rth_env_actor_step(rth_nstep *h, const rth_env_actor_args *args, void *stream);
 

@@ -276,7 +276,7 @@ SIGNATURES = {
                                      c_i64, c_i64, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "rth_soft_update": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_f64,
                                 c_vp]),
-    # the CartPole actors on the MLP kernels (mlp_actor.hpp)
+    # the CartPole actors on the MLP kernels (mlp_actor.hpp: adapters onto the step below)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),
     "rth_mlp_actor_step": (c_i32, [c_vp, ctypes.POINTER(MlpActorArgs), c_vp]),
     # the classic-control family on the same step (env_actor.hpp)

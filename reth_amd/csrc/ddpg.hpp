@@ -19,20 +19,18 @@
 // second launch, over the activations and pre-activation gradients the first left in the
 // workspace.
 //
-// Every product is one fmaf.  A dot product over k has ONE summation order -- ddpg_dense and
-// ddpg_head share it --: term k goes to accumulator k % 8 in increasing k, the eight are added as
-// ((0+1)+(2+3))+((4+5)+(6+7)), then the bias; zero padding adds nothing.  A row's result does not
-// depend on B, on its position, on the grid or on the entry point.  The batch sums go row b to
-// accumulator b % 4 in increasing b, then (0+1)+(2+3), per output element: no atomics.
+// Every product is one fmaf.  A dot product over k has ONE summation order -- dense.hpp's, which
+// ddpg_dense and ddpg_head share --, then the bias; zero padding adds nothing.  A row's result does
+// not depend on B, on its position, on the grid or on the entry point.  The batch sums are
+// dense.hpp's, in its order: no atomics.
 #pragma once
-#include "common.hpp"
-#include "mlp.hpp"  // mlp_relu, mlp_tree8, mlp_fma8
+#include "dense.hpp"
 
 namespace rth {
 
-constexpr int kDdpgMaxD = 64, kDdpgMaxAd = 8, kDdpgMaxH = 512;
-constexpr int kDdpgRows = 8;       // rows per tile
-constexpr int kDdpgThreads = 256;  // lane j = tid % 128: output unit of a pass; tid / 128: which 4 of the tile's rows
+constexpr int kDdpgMaxD = kDenseMaxD, kDdpgMaxAd = 8, kDdpgMaxH = 512;
+constexpr int kDdpgRows = kDenseRows;        // rows per tile
+constexpr int kDdpgThreads = kDenseThreads;  // lane j = tid % 128: output unit of a pass; tid / 128: which 4 of the tile's rows
 constexpr int kDdpgNT = 128, kDdpgRpt = kDdpgRows / (kDdpgThreads / kDdpgNT);
 constexpr int kDdpgKT = 32;                // reduction length of one staged chunk
 constexpr int kDdpgLdW = kDdpgKT + 4;      // row stride of a forward chunk [128 units][32 k]
@@ -40,19 +38,10 @@ constexpr int kDdpgLdT = kDdpgNT + 4;      // ... of a transposed chunk [32 n][1
 constexpr int kDdpgChunk = kDdpgNT * kDdpgLdW;
 constexpr int kDdpgPer = kDdpgNT * kDdpgKT / kDdpgThreads;  // chunk elements a lane fetches
 constexpr int kDdpgLdH = kDdpgMaxH + kDdpgMaxAd;            // row stride of the activations in LDS
-constexpr int kDdpgMaxBlocks = 1024;
-constexpr int kDdpgGradThreads = 128, kDdpgGradJ = 4;  // second launch: 4 output rows x 128 columns per workgroup
 static_assert(kDdpgChunk >= kDdpgKT * kDdpgLdT, "the transposed chunk fits in the staging buffer");
 static_assert(kDdpgRows * kDdpgMaxAd <= kDdpgThreads, "one lane per (row, action component)");
 
-struct DdpgNet {  // fc1.weight [H1, D], fc1.bias, fc2.weight [H2, H1 (+ Ad)], fc2.bias, fc3.weight [Ad | 1, H2], fc3.bias
-  const float *w1, *b1, *w2, *b2, *w3, *b3;
-};
-
-struct DdpgGrads {
-  float *w1, *b1, *w2, *b2, *w3, *b3;
-};
-
+// a network (DenseNet): fc1.weight [H1, D], fc1.bias, fc2.weight [H2, H1 (+ Ad)], fc2.bias, fc3.weight [Ad | 1, H2], fc3.bias
 struct DdpgDims {
   int D, Ad, H1, H2;
 };
@@ -83,16 +72,6 @@ struct DdpgWs {
     return B * (2 * Ad + 1 + (H1 + Ad) + 2 * H2 + H1);
   }
 };
-
-// rows [r0, r0 + kDdpgRows) of x [n, D] (row stride ldx) into s.x, zero past n and past D: nothing
-// outside [0, n) x [0, D) is read.  No barrier.
-__device__ inline void ddpg_load_x(const float *__restrict__ x, int64_t ldx, int64_t n, int64_t r0, int D,
-                                   DdpgSmem &s) {
-  for (int i = threadIdx.x; i < kDdpgRows * kDdpgMaxD; i += kDdpgThreads) {
-    const int r = i / kDdpgMaxD, k = i % kDdpgMaxD;
-    s.x[r][k] = (r0 + r < n && k < D) ? x[(r0 + r) * ldx + k] : 0.0f;
-  }
-}
 
 // out[r][n] = act(sum_k in[r][k] W[n][k] + bias[n]) for the tile's rows: W [N, K] dense in global
 // memory (any alignment), in / out LDS rows (strides multiples of 4; in's columns [K, round-up-8(K))
@@ -138,7 +117,7 @@ __device__ inline void ddpg_dense(const float *__restrict__ W, const float *__re
           const float *xr = in + (rb + rr) * ldin + k0 + kk;
           const float4 xa = *reinterpret_cast<const float4 *>(xr);
           const float4 xb = *reinterpret_cast<const float4 *>(xr + 4);
-          mlp_fma8(xa, xb, wa, wb, acc[rr]);
+          dense_fma8(xa, xb, wa, wb, acc[rr]);
         }
       }
     }
@@ -146,8 +125,8 @@ __device__ inline void ddpg_dense(const float *__restrict__ W, const float *__re
       const float b = bias[n0 + j];
 #pragma unroll
       for (int rr = 0; rr < kDdpgRpt; ++rr) {
-        const float val = radd(mlp_tree8(acc[rr]), b);
-        out[(rb + rr) * ldout + n0 + j] = relu ? mlp_relu(val) : val;
+        const float val = radd(dense_tree8(acc[rr]), b);
+        out[(rb + rr) * ldout + n0 + j] = relu ? dense_relu(val) : val;
       }
     }
   }
@@ -202,7 +181,7 @@ __device__ inline void ddpg_dense_t(const float *__restrict__ W, int ldw, int N,
           const float *gr = g + (rb + rr) * ldg + n0 + nn;
           const float4 ga = *reinterpret_cast<const float4 *>(gr);
           const float4 gb = *reinterpret_cast<const float4 *>(gr + 4);
-          mlp_fma8(ga, gb, wa, wb, acc[rr]);
+          dense_fma8(ga, gb, wa, wb, acc[rr]);
         }
       }
     }
@@ -210,7 +189,7 @@ __device__ inline void ddpg_dense_t(const float *__restrict__ W, int ldw, int N,
 #pragma unroll
       for (int rr = 0; rr < kDdpgRpt; ++rr) {
         const int r = rb + rr;
-        if (r0 + r < B) out[(r0 + r) * ldo + kb + j] = mask[r * ldm + kb + j] > 0.0f ? mlp_tree8(acc[rr]) : 0.0f;
+        if (r0 + r < B) out[(r0 + r) * ldo + kb + j] = mask[r * ldm + kb + j] > 0.0f ? dense_tree8(acc[rr]) : 0.0f;
       }
     }
   }
@@ -240,7 +219,7 @@ __device__ inline void ddpg_head(const float *__restrict__ W, int64_t sa, int64_
     float p[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) p[i] = s.part[o * 8 + i];
-    const float val = mlp_tree8(p);
+    const float val = dense_tree8(p);
     out[r * ldout + a] = bias ? radd(val, bias[a]) : val;
   }
   __syncthreads();
@@ -248,7 +227,7 @@ __device__ inline void ddpg_head(const float *__restrict__ W, int64_t sa, int64_
 
 // The actor's forward of the rows in s.x: the hidden activations to h1b / h2b (LDS, stride
 // kDdpgLdH), the head to s.pre, its tanh -- in fp64, rounded once -- to s.act.  The only actor forward.
-__device__ inline void ddpg_actor_forward(const DdpgNet &p, const DdpgDims &d, float *h1b, float *h2b, DdpgSmem &s) {
+__device__ inline void ddpg_actor_forward(const DenseNet &p, const DdpgDims &d, float *h1b, float *h2b, DdpgSmem &s) {
   ddpg_dense(p.w1, p.b1, d.H1, d.D, &s.x[0][0], kDdpgMaxD, h1b, kDdpgLdH, true, s);
   ddpg_dense(p.w2, p.b2, d.H2, d.H1, h1b, kDdpgLdH, h2b, kDdpgLdH, true, s);
   ddpg_head(p.w3, d.H2, 1, p.b3, d.Ad, d.H2, h2b, kDdpgLdH, &s.pre[0][0], kDdpgMaxAd, s);
@@ -262,7 +241,7 @@ __device__ inline void ddpg_actor_forward(const DdpgNet &p, const DdpgDims &d, f
 
 // The critic's forward of the rows in s.x with the actions a (LDS rows of stride kDdpgMaxAd):
 // cat(h1, a) to s.h1, h2 to s.h2, Q to q.
-__device__ inline void ddpg_critic_forward(const DdpgNet &p, const DdpgDims &d, const float *a, float *q, DdpgSmem &s) {
+__device__ inline void ddpg_critic_forward(const DenseNet &p, const DdpgDims &d, const float *a, float *q, DdpgSmem &s) {
   ddpg_dense(p.w1, p.b1, d.H1, d.D, &s.x[0][0], kDdpgMaxD, &s.h1[0][0], kDdpgLdH, true, s);
   const int tid = threadIdx.x;
   if (tid < kDdpgRows * d.Ad) {
@@ -282,14 +261,14 @@ __device__ inline void ddpg_store_rows(const float *src, int cols, float *__rest
   }
 }
 
-__global__ __launch_bounds__(kDdpgThreads) void k_ddpg_act(DdpgNet p, const float *__restrict__ x, int64_t ldx,
+__global__ __launch_bounds__(kDdpgThreads) void k_ddpg_act(DenseNet p, const float *__restrict__ x, int64_t ldx,
                                                            int64_t n, DdpgDims d, float *__restrict__ out) {
   __shared__ __align__(16) DdpgSmem s;
   const int64_t tiles = (n + kDdpgRows - 1) / kDdpgRows;
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t r0 = t * kDdpgRows;
     __syncthreads();
-    ddpg_load_x(x, ldx, n, r0, d.D, s);
+    dense_load_x(x, ldx, n, r0, d.D, s.x);
     ddpg_actor_forward(p, d, &s.h1[0][0], &s.h2[0][0], s);
     const int tid = threadIdx.x;
     if (tid < kDdpgRows * d.Ad) {
@@ -304,7 +283,7 @@ __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_act(DdpgNet p, const floa
 // element, dQ) and -- backward -- the critic's data gradients; cat(h1, a), h2 and the
 // pre-activation gradients go to the workspace for the second launch.
 __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_critic(
-    DdpgNet cr, DdpgNet at, DdpgNet ct, const float *__restrict__ s0, int64_t lds0, const float *__restrict__ a,
+    DenseNet cr, DenseNet at, DenseNet ct, const float *__restrict__ s0, int64_t lds0, const float *__restrict__ a,
     int64_t lda, const float *__restrict__ rew, const float *__restrict__ done, const float *__restrict__ s1,
     int64_t lds1, const float *__restrict__ isw, int64_t B, DdpgDims d, float gamma, int backward,
     float *__restrict__ wsp, float *__restrict__ td_abs) {
@@ -317,10 +296,10 @@ __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_critic(
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t r0 = t * kDdpgRows;
     __syncthreads();
-    ddpg_load_x(s1, lds1, B, r0, d.D, s);
+    dense_load_x(s1, lds1, B, r0, d.D, s.x);
     ddpg_actor_forward(at, d, &s.h1[0][0], &s.h2[0][0], s);
     ddpg_critic_forward(ct, d, &s.act[0][0], s.q1, s);
-    ddpg_load_x(s0, lds0, B, r0, d.D, s);
+    dense_load_x(s0, lds0, B, r0, d.D, s.x);
     if (tid < kDdpgRows * d.Ad) {
       const int r = tid / d.Ad, c = tid % d.Ad;
       s.pre[r][c] = r0 + r < B ? a[(r0 + r) * lda + c] : 0.0f;
@@ -366,7 +345,7 @@ __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_critic(
 // through the critic's last layer, its middle layer's ReLU and the action columns [H1, H1 + Ad) of
 // its middle weight, through 1 - tanh^2, then the actor's data gradients.  The action, the actor's
 // activations and pre-activation gradients go to the workspace for the second launch.
-__global__ __launch_bounds__(kDdpgThreads) void k_ddpg_actor(DdpgNet ac, DdpgNet cr, const float *__restrict__ s0,
+__global__ __launch_bounds__(kDdpgThreads) void k_ddpg_actor(DenseNet ac, DenseNet cr, const float *__restrict__ s0,
                                                              int64_t lds0, int64_t B, DdpgDims d,
                                                              float *__restrict__ wsp) {
   __shared__ __align__(16) DdpgSmem s;
@@ -378,7 +357,7 @@ __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_actor(DdpgNet ac, DdpgNet
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t r0 = t * kDdpgRows;
     __syncthreads();
-    ddpg_load_x(s0, lds0, B, r0, d.D, s);
+    dense_load_x(s0, lds0, B, r0, d.D, s.x);
     ddpg_actor_forward(ac, d, &s.ah1[0][0], &s.ah2[0][0], s);
     ddpg_critic_forward(cr, d, &s.act[0][0], s.q, s);
     // the critic's layer 3 and ReLU: g2 = (h2 > 0) ? -1/B W3 : 0
@@ -416,107 +395,49 @@ __global__ __launch_bounds__(kDdpgThreads) void k_ddpg_actor(DdpgNet ac, DdpgNet
   }
 }
 
-// gw[n][k] = sum_b G[b][n] X[b][k] for the rows n in [n0, n0 + kDdpgGradJ) and the columns
-// k = k0 + lane of one layer: row b to accumulator b % 4
-__device__ inline void ddpg_wgrad_tile(const float *__restrict__ G, int64_t ldg, int N, const float *__restrict__ X,
-                                       int64_t ldx, int K, int64_t B, int n0, int k0, float *__restrict__ gw) {
-  const int k = k0 + (int)threadIdx.x;
-  if (k >= K) return;
-  float acc[kDdpgGradJ][4] = {};
-  int nn[kDdpgGradJ];
-#pragma unroll
-  for (int i = 0; i < kDdpgGradJ; ++i) nn[i] = n0 + i < N ? n0 + i : N - 1;  // clamped: read in bounds, not stored
-  int64_t b = 0;
-#pragma unroll 4
-  for (; b + 4 <= B; b += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float x = X[(b + u) * ldx + k];
-#pragma unroll
-      for (int i = 0; i < kDdpgGradJ; ++i) acc[i][u] = fmaf(G[(b + u) * ldg + nn[i]], x, acc[i][u]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    if (b + u < B) {
-      const float x = X[(b + u) * ldx + k];
-#pragma unroll
-      for (int i = 0; i < kDdpgGradJ; ++i) acc[i][u] = fmaf(G[(b + u) * ldg + nn[i]], x, acc[i][u]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < kDdpgGradJ; ++i)
-    if (n0 + i < N) gw[(int64_t)(n0 + i) * K + k] = radd(radd(acc[i][0], acc[i][1]), radd(acc[i][2], acc[i][3]));
-}
-
-// gb[n] = sum_b G[b][n], n = n0 + lane, the same order over b
-__device__ inline void ddpg_bgrad(const float *__restrict__ G, int64_t ldg, int N, int64_t B, int n0,
-                                  float *__restrict__ gb) {
-  const int n = n0 + (int)threadIdx.x;
-  if (n >= N) return;
-  float acc[4] = {};
-  int64_t b = 0;
-#pragma unroll 4
-  for (; b + 4 <= B; b += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = radd(acc[u], G[(b + u) * ldg + n]);
-  }
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-    if (b + u < B) acc[u] = radd(acc[u], G[(b + u) * ldg + n]);
-  gb[n] = radd(radd(acc[0], acc[1]), radd(acc[2], acc[3]));
-}
-
 // the second launch's workgroups: the middle layer's weight gradient ([H2, Kw2], Kw2 = H1 + Ad for
 // the critic, H1 for the actor), the first layer's, the last layer's ([N3, H2]), the three bias
 // gradients, then one workgroup for the loss mean
 struct DdpgWgradPlan {
   int kt2, t2, t1, kt3, t3, nb1, nb2;
   __host__ __device__ DdpgWgradPlan(const DdpgDims &d, int Kw2, int N3) {
-    kt2 = (Kw2 + kDdpgGradThreads - 1) / kDdpgGradThreads;
-    t2 = (d.H2 + kDdpgGradJ - 1) / kDdpgGradJ * kt2;
-    t1 = (d.H1 + kDdpgGradJ - 1) / kDdpgGradJ;
-    kt3 = (d.H2 + kDdpgGradThreads - 1) / kDdpgGradThreads;
-    t3 = (N3 + kDdpgGradJ - 1) / kDdpgGradJ * kt3;
-    nb1 = (d.H1 + kDdpgGradThreads - 1) / kDdpgGradThreads;
-    nb2 = (d.H2 + kDdpgGradThreads - 1) / kDdpgGradThreads;
+    kt2 = (Kw2 + kDenseGradThreads - 1) / kDenseGradThreads;
+    t2 = (d.H2 + kDenseGradJ - 1) / kDenseGradJ * kt2;
+    t1 = (d.H1 + kDenseGradJ - 1) / kDenseGradJ;
+    kt3 = (d.H2 + kDenseGradThreads - 1) / kDenseGradThreads;
+    t3 = (N3 + kDenseGradJ - 1) / kDenseGradJ * kt3;
+    nb1 = (d.H1 + kDenseGradThreads - 1) / kDenseGradThreads;
+    nb2 = (d.H2 + kDenseGradThreads - 1) / kDenseGradThreads;
   }
   __host__ __device__ int grad_blocks() const { return t2 + t1 + t3 + nb1 + nb2 + 1; }
 };
 
-__global__ __launch_bounds__(kDdpgGradThreads) void k_ddpg_wgrad(DdpgGrads g, const float *__restrict__ s0,
+__global__ __launch_bounds__(kDenseGradThreads) void k_ddpg_wgrad(DenseGrads g, const float *__restrict__ s0,
                                                                  int64_t lds0, int64_t B, DdpgDims d, int Kw2, int N3,
                                                                  float *__restrict__ wsp, float *__restrict__ loss,
                                                                  int first) {
-  __shared__ float part[kDdpgGradThreads];
+  __shared__ float part[kDenseGradThreads];
   const DdpgWs ws(wsp, B, d);
   const DdpgWgradPlan pl(d, Kw2, N3);
   const int K2 = d.H1 + d.Ad;
   int blk = (int)blockIdx.x + first;
   if (blk < pl.t2)
-    return ddpg_wgrad_tile(ws.g2, d.H2, d.H2, ws.xc, K2, Kw2, B, blk / pl.kt2 * kDdpgGradJ,
-                           blk % pl.kt2 * kDdpgGradThreads, g.w2);
+    return dense_wgrad_tile(ws.g2, d.H2, d.H2, ws.xc, K2, Kw2, B, blk / pl.kt2 * kDenseGradJ,
+                           blk % pl.kt2 * kDenseGradThreads, g.w2);
   blk -= pl.t2;
-  if (blk < pl.t1) return ddpg_wgrad_tile(ws.g1, d.H1, d.H1, s0, lds0, d.D, B, blk * kDdpgGradJ, 0, g.w1);
+  if (blk < pl.t1) return dense_wgrad_tile(ws.g1, d.H1, d.H1, s0, lds0, d.D, B, blk * kDenseGradJ, 0, g.w1);
   blk -= pl.t1;
   if (blk < pl.t3)
-    return ddpg_wgrad_tile(ws.g3, N3, N3, ws.h2, d.H2, d.H2, B, blk / pl.kt3 * kDdpgGradJ,
-                           blk % pl.kt3 * kDdpgGradThreads, g.w3);
+    return dense_wgrad_tile(ws.g3, N3, N3, ws.h2, d.H2, d.H2, B, blk / pl.kt3 * kDenseGradJ,
+                           blk % pl.kt3 * kDenseGradThreads, g.w3);
   blk -= pl.t3;
-  if (blk < pl.nb1) return ddpg_bgrad(ws.g1, d.H1, d.H1, B, blk * kDdpgGradThreads, g.b1);
+  if (blk < pl.nb1) return dense_bgrad(ws.g1, d.H1, d.H1, B, blk * kDenseGradThreads, g.b1);
   blk -= pl.nb1;
-  if (blk < pl.nb2) return ddpg_bgrad(ws.g2, d.H2, d.H2, B, blk * kDdpgGradThreads, g.b2);
+  if (blk < pl.nb2) return dense_bgrad(ws.g2, d.H2, d.H2, B, blk * kDenseGradThreads, g.b2);
   blk -= pl.nb2;
-  if (blk == 0) return ddpg_bgrad(ws.g3, N3, N3, B, 0, g.b3);
-  float acc = 0.0f;  // the loss mean: per-lane sums in index order, then an LDS tree
-  for (int64_t b = threadIdx.x; b < B; b += kDdpgGradThreads) acc = radd(acc, ws.le[b]);
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int st = kDdpgGradThreads / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) part[threadIdx.x] = radd(part[threadIdx.x], part[threadIdx.x + st]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) loss[0] = part[0] / (float)B;
+  if (blk == 0) return dense_bgrad(ws.g3, N3, N3, B, 0, g.b3);
+  const float sum = dense_loss_sum(ws.le, B, part);
+  if (threadIdx.x == 0 && loss) loss[0] = sum / (float)B;
 }
 
 // rth_soft_update: every tensor of a network in one launch, kSoftPer elements per workgroup
@@ -549,19 +470,6 @@ inline bool ddpg_shape_ok(int64_t D, int64_t Ad, int64_t H1, int64_t H2) {
          H2 >= 4 && H2 <= kDdpgMaxH && H2 % 4 == 0;
 }
 
-inline bool ddpg_net(const float *const *params, DdpgNet *out) {
-  if (!params) return false;
-  for (int i = 0; i < 6; ++i)
-    if (!params[i]) return false;
-  *out = DdpgNet{params[0], params[1], params[2], params[3], params[4], params[5]};
-  return true;
-}
-
-inline unsigned ddpg_grid(int64_t rows) {
-  const int64_t tiles = (rows + kDdpgRows - 1) / kDdpgRows;
-  return (unsigned)(tiles < kDdpgMaxBlocks ? tiles : kDdpgMaxBlocks);
-}
-
 #define RTH_DDPG_LIMITS "(D in 1..64, Ad in 1..8, H1 and H2 multiples of 4 in 4..512)"
 #define RTH_DDPG_SHAPE(fn)                                                                                    \
   RTH_REQUIRE(ddpg_shape_ok(D, Ad, H1, H2), fn ": unsupported shape D=%lld Ad=%lld H1=%lld H2=%lld " RTH_DDPG_LIMITS, \
@@ -589,10 +497,10 @@ int rth_ddpg_act(const float *const *actor, const float *x_dev, int64_t ldx, int
   RTH_DDPG_SHAPE("rth_ddpg_act");
   RTH_REQUIRE(n >= 1 && n <= (int64_t)1 << 40 && ldx >= D, "rth_ddpg_act: bad n=%lld or ldx=%lld < D=%lld",
               (long long)n, (long long)ldx, (long long)D);
-  DdpgNet p;
-  RTH_REQUIRE(ddpg_net(actor, &p) && x_dev && act_out_dev, "rth_ddpg_act: NULL argument");
+  DenseNet p;
+  RTH_REQUIRE(dense_net(actor, &p) && x_dev && act_out_dev, "rth_ddpg_act: NULL argument");
   const DdpgDims d{(int)D, (int)Ad, (int)H1, (int)H2};
-  hipLaunchKernelGGL(k_ddpg_act, dim3(ddpg_grid(n)), dim3(kDdpgThreads), 0, as_stream(stream), p, x_dev, ldx, n, d,
+  hipLaunchKernelGGL(k_ddpg_act, dim3(dense_grid(n)), dim3(kDdpgThreads), 0, as_stream(stream), p, x_dev, ldx, n, d,
                      act_out_dev);
   RTH_LAUNCHED();
   return RTH_OK;
@@ -608,29 +516,29 @@ int rth_ddpg_critic_grads(const float *const *critic, const float *const *actor_
   RTH_REQUIRE(B >= 1 && B <= (int64_t)1 << 40 && lds0 >= D && lds1 >= D && lda >= Ad,
               "rth_ddpg_critic_grads: bad B=%lld or row stride (%lld, %lld) < D=%lld, %lld < Ad=%lld", (long long)B,
               (long long)lds0, (long long)lds1, (long long)D, (long long)lda, (long long)Ad);
-  DdpgNet cr, at, ct;
-  RTH_REQUIRE(ddpg_net(critic, &cr) && ddpg_net(actor_target, &at) && ddpg_net(critic_target, &ct) && s0_dev &&
+  DenseNet cr, at, ct;
+  RTH_REQUIRE(dense_net(critic, &cr) && dense_net(actor_target, &at) && dense_net(critic_target, &ct) && s0_dev &&
                   a_dev && r_dev && done_dev && s1_dev && workspace_dev,
               "rth_ddpg_critic_grads: NULL argument");
-  DdpgGrads g{};
+  DenseGrads g{};
   if (grads) {
     for (int i = 0; i < 6; ++i) RTH_REQUIRE(grads[i], "rth_ddpg_critic_grads: NULL gradient buffer %d", i);
-    g = DdpgGrads{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
+    g = DenseGrads{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
   }
   const DdpgDims d{(int)D, (int)Ad, (int)H1, (int)H2};
   float *ws = static_cast<float *>(workspace_dev);
-  hipLaunchKernelGGL(k_ddpg_critic, dim3(ddpg_grid(B)), dim3(kDdpgThreads), 0, as_stream(stream), cr, at, ct, s0_dev,
+  hipLaunchKernelGGL(k_ddpg_critic, dim3(dense_grid(B)), dim3(kDdpgThreads), 0, as_stream(stream), cr, at, ct, s0_dev,
                      lds0, a_dev, lda, r_dev, done_dev, s1_dev, lds1, isw_dev, B, d, gamma, (int)(grads != nullptr), ws,
                      td_abs_dev);
   RTH_LAUNCHED();
   const int Kw2 = (int)(H1 + Ad);
   const int grad_blocks = DdpgWgradPlan(d, Kw2, 1).grad_blocks();
   if (grads) {  // every gradient element, then the loss mean
-    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(grad_blocks + 1), dim3(kDdpgGradThreads), 0, as_stream(stream), g, s0_dev,
+    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(grad_blocks + 1), dim3(kDenseGradThreads), 0, as_stream(stream), g, s0_dev,
                        lds0, B, d, Kw2, 1, ws, loss_dev, 0);
     RTH_LAUNCHED();
   } else if (loss_dev) {
-    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(1), dim3(kDdpgGradThreads), 0, as_stream(stream), g, s0_dev, lds0, B, d, Kw2,
+    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(1), dim3(kDenseGradThreads), 0, as_stream(stream), g, s0_dev, lds0, B, d, Kw2,
                        1, ws, loss_dev, grad_blocks);
     RTH_LAUNCHED();
   }
@@ -644,18 +552,18 @@ int rth_ddpg_actor_grads(const float *const *actor, const float *const *critic, 
   RTH_DDPG_SHAPE("rth_ddpg_actor_grads");
   RTH_REQUIRE(B >= 1 && B <= (int64_t)1 << 40 && lds0 >= D, "rth_ddpg_actor_grads: bad B=%lld or row stride %lld < D=%lld",
               (long long)B, (long long)lds0, (long long)D);
-  DdpgNet ac, cr;
-  RTH_REQUIRE(ddpg_net(actor, &ac) && ddpg_net(critic, &cr) && s0_dev && workspace_dev && grads,
+  DenseNet ac, cr;
+  RTH_REQUIRE(dense_net(actor, &ac) && dense_net(critic, &cr) && s0_dev && workspace_dev && grads,
               "rth_ddpg_actor_grads: NULL argument");
   for (int i = 0; i < 6; ++i) RTH_REQUIRE(grads[i], "rth_ddpg_actor_grads: NULL gradient buffer %d", i);
-  const DdpgGrads g{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
+  const DenseGrads g{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
   const DdpgDims d{(int)D, (int)Ad, (int)H1, (int)H2};
   float *ws = static_cast<float *>(workspace_dev);
-  hipLaunchKernelGGL(k_ddpg_actor, dim3(ddpg_grid(B)), dim3(kDdpgThreads), 0, as_stream(stream), ac, cr, s0_dev, lds0,
+  hipLaunchKernelGGL(k_ddpg_actor, dim3(dense_grid(B)), dim3(kDdpgThreads), 0, as_stream(stream), ac, cr, s0_dev, lds0,
                      B, d, ws);
   RTH_LAUNCHED();
   const int grad_blocks = DdpgWgradPlan(d, (int)H1, (int)Ad).grad_blocks();
-  hipLaunchKernelGGL(k_ddpg_wgrad, dim3(grad_blocks + 1), dim3(kDdpgGradThreads), 0, as_stream(stream), g, s0_dev, lds0,
+  hipLaunchKernelGGL(k_ddpg_wgrad, dim3(grad_blocks + 1), dim3(kDenseGradThreads), 0, as_stream(stream), g, s0_dev, lds0,
                      B, d, (int)H1, (int)Ad, ws, loss_dev, 0);
   RTH_LAUNCHED();
   return RTH_OK;

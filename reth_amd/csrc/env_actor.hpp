@@ -1,18 +1,21 @@
-// Device-resident classic-control actors on the fused MLP kernels: mlp_actor.hpp's one launch per
-// env step (rth_env_actor_step), generic over a small family of environments -- CartPole-v0/v1,
-// Acrobot-v1 and MountainCar-v0 -- each at its own network shape (D, A).  The kernel is templated on
-// the env id; per tile of kMlpRows rows it runs the acting forward of mlp.hpp at the env's (D, A)
+// Device-resident classic-control actors on the fused MLP kernels: one launch per env step for N
+// actors, generic over a small family of environments -- CartPole-v0/v1, Acrobot-v1 and
+// MountainCar-v0 -- each at its own network shape (D, A).  ONE step kernel and ONE reset kernel,
+// templated on the env id, behind four entry points: rth_env_reset / rth_env_actor_step (any env,
+// here) and rth_cartpole_reset / rth_mlp_actor_step (mlp_actor.hpp: adapters that launch the
+// CartPole instance without return statistics; same bits, pinned by
+// tests/test_classic_actors_gpu.py::test_generic_cartpole_equals_the_cartpole_actors).
+// Per tile of kMlpRows rows the step runs the acting forward of mlp.hpp at the env's (D, A)
 // (mlp_forward_rows, the only forward: a row's Q equals rth_mlp_q's bit for bit), then one lane per
 // env: ε-greedy with the draws of eps_greedy_one, the env's dynamics in fp64 in its host class's
 // operation order (reth_amd/envs.py: CartPole, Acrobot, MountainCar), the time limit, the reset of
-// a finished episode, the f32 observation into a per-env ring, the n-step push (nstep_push_one)
-// and the emitted row by handle and by value.  No host synchronisation, no atomics: everything
-// an env touches is private to its lane.  rth_mlp_actor_step stays as it is; with env = CartPole
-// this entry point computes the same bits (it calls the same device functions).
+// a finished episode, the f32 observation into a per-env ring, the n-step push (nstep_push_one on
+// an rth_nstep handle) and the emitted row by handle and by value.  No host synchronisation, no
+// atomics: everything an env touches is private to its lane.
 //
-// Reference: reth/reth/presets/worker.py:128-155 (Worker.step), utils/exploration.py:26-31,
-// algorithm/dqn/dqn_solver.py:126-131, utils/nstep_adder.py:11-28; the environments restate gym
-// 0.17.3's classic_control definitions (the reference's pinned dependency).
+// Reference: reth/reth/presets/worker.py:128-155 (Worker.step: act, env.step, env.reset on done),
+// utils/exploration.py:26-31, algorithm/dqn/dqn_solver.py:126-131, utils/nstep_adder.py:11-28; the
+// environments restate gym 0.17.3's classic_control definitions (the reference's pinned dependency).
 //
 // Environments (include/reth_hip.h: RTH_ENV_*), state fp64 [N, 4] with unused columns 0:
 //   CARTPOLE     D 4, A 2  state (x, x_dot, theta, theta_dot)   obs = state          reward 1
@@ -21,40 +24,46 @@
 //   MOUNTAINCAR  D 2, A 3  state (p, v, 0, 0)                   obs = (p, v)         reward -1
 // The time limit ends an episode without changing its reward.
 //
-// Step counter, ε-greedy draws: as mlp_actor.hpp (t = t_dev[i] + 1, eps_explore_draw at counter t).
+// Step counter.  t_dev is int64 [N]: every env carries the (common) number of env steps taken and
+// advances its own copy, t = t_dev[i] + 1, so the one launch needs no grid-wide agreement on who
+// increments a scalar.  ε-greedy at step t draws with counter = t, lane = i (eps_explore_draw).
 //
-// Reset draws (rth_env_reset at t = 0, and step t of an env whose episode ended at t): one
-// Philox4x32-10 block per (seed, env i, t),
+// Reset draws (the reset entry points at t = 0, and step t of an env whose episode ended at t): one
+// Philox4x32-10 block per (seed, env i, t) -- a pure function of the three --,
 //     counter = {(uint32) i, (uint32) t, (uint32) (t >> 32), stream}
 //     key     = {(uint32) seed, (uint32) (seed >> 32)}
 // with stream = STREAM_CARTPOLE (7), STREAM_ACROBOT (9), STREAM_MOUNTAINCAR (10), and with the
 // four output words c[k], in fp64 with each operation rounded once:
-//     CartPole     state[k] = -0.05 + (0.1 * (double) c[k]) / 2^32   k = 0..3  (mlp_actor.hpp's)
+//     CartPole     state[k] = -0.05 + (0.1 * (double) c[k]) / 2^32   k = 0..3, in [-0.05, 0.05)
 //     Acrobot      state[k] = -0.1  + (0.2 * (double) c[k]) / 2^32   k = 0..3, in [-0.1, 0.1)
 //     MountainCar  p        = -0.6  + (0.2 * (double) c[0]) / 2^32   in [-0.6, -0.4);  v = 0
 //
 // Observation ring.  f32 [N * ring + 1, LD], LD = D rounded up to 4 floats (CartPole 4, Acrobot 8,
 // MountainCar 4) so a row moves as 16-byte pieces; the pad floats are written as 0; the last row
-// is an all-zero sink the kernel never writes.  Slots and handles as mlp_actor.hpp: env i's slot
-// s at row i * ring + s = the handle; step t writes the next observation into slot (2t) % ring
-// and a reset observation into (2t + 1) % ring; ring >= 2 (n + 2).  row_obs0 / row_obs1 are dense
-// [N, D] (D is even for every env: 8-byte pieces).
+// is an all-zero sink the kernel never writes.  Env i's slot s is row i * ring + s = the handle.
+// Step t writes the next observation into slot (2t) % ring and, when the episode ended, the reset
+// observation into (2t + 1) % ring; cur_slot[i] is the slot of the observation the env acts on
+// next.  A done row's s1 is the terminal observation.  An emitted n-step row references slots
+// written at most n + 1 steps earlier, so ring >= 2 (n + 2) keeps them intact for the by-value
+// copy.  row_obs0 / row_obs1 are dense [N, D] (D is even for every env: 8-byte pieces).
 //
 // Statistics.  stats int64 [N, 3]: finished episodes, the sum of their lengths, the last length.
-// ret_stats fp64 [N, 3]: the running episode's return, the sum of the finished episodes' returns,
-// the last finished return (rewards are small integers, so the sums are exact).
+// ret_stats fp64 [N, 3], NULL from the CartPole adapters (the return is the length there): the
+// running episode's return, the sum of the finished episodes' returns, the last finished return
+// (rewards are small integers, so the sums are exact).
 #pragma once
-#include "mlp_actor.hpp"
+#include "actor_shared.hpp"
+#include "mlp.hpp"
 
 namespace rth {
 
-constexpr uint32_t STREAM_ACROBOT = 9u, STREAM_MOUNTAINCAR = 10u;
+constexpr uint32_t STREAM_CARTPOLE = 7u, STREAM_ACROBOT = 9u, STREAM_MOUNTAINCAR = 10u;
 
 template <int ENV>
 struct EnvSpec;
 template <>
 struct EnvSpec<RTH_ENV_CARTPOLE> {
-  static constexpr int D = kCartD, A = kCartA;
+  static constexpr int D = 4, A = 2;
 };
 template <>
 struct EnvSpec<RTH_ENV_ACROBOT> {
@@ -67,9 +76,64 @@ struct EnvSpec<RTH_ENV_MOUNTAINCAR> {
 constexpr int env_ld(int D) { return (D + 3) & ~3; }  // the ring's row stride in floats
 
 struct EnvActor {
-  MlpActor m;
-  double *ret_stats;
+  DenseNet net;
+  double *state;
+  int32_t *ep_steps;
+  int64_t *t_dev, *stats;
+  double *ret_stats;  // NULL: no return statistics (workgroup-uniform)
+  float *obs_ring;
+  int64_t *cur_slot;
+  const double *eps;
+  const int64_t *action_in;
+  int64_t *action;
+  float *reward, *done;
+  int64_t *s0_h, *s1_h;
+  int32_t *emit;
+  int64_t *row_s0, *row_a, *row_s1;
+  float *row_r, *row_done, *row_obs0, *row_obs1, *q_out;
+  uint64_t seed;
+  int64_t N;
+  int ring, max_steps;
+  NStepState ns;
+  int n;
+  double gamma;
+  int mode;
 };
+
+// ------------------------------------------------------------------ CartPole
+__device__ inline void cartpole_reset_draw(uint64_t seed, int64_t i, int64_t t, double (&s)[4]) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_CARTPOLE};
+  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = radd(-0.05, rmul(0.1, (double)c[k]) / 4294967296.0);
+}
+
+__device__ __forceinline__ float4 cartpole_obs(const double (&s)[4]) {
+  return make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
+}
+
+// envs.CartPole.step (gym 0.17.3 classic_control/cartpole.py, Euler): every product and sum
+// rounded where python rounds it, squares as products; returns the terminal test on x / theta
+__device__ inline bool cartpole_dynamics(double (&s)[4], int64_t action) {
+  const double gravity = 9.8, masscart = 1.0, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
+  const double theta_threshold = 12 * 2 * 3.141592653589793 / 360, x_threshold = 2.4;
+  double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+  const double force = action == 1 ? force_mag : -force_mag;
+  const double costheta = cos(theta), sintheta = sin(theta);
+  const double total_mass = radd(masspole, masscart);
+  const double polemass_length = rmul(masspole, length);
+  const double temp = radd(force, rmul(rmul(polemass_length, rmul(theta_dot, theta_dot)), sintheta)) / total_mass;
+  const double thetaacc =
+      rsub(rmul(gravity, sintheta), rmul(costheta, temp)) /
+      rmul(length, rsub(4.0 / 3.0, rmul(masspole, rmul(costheta, costheta)) / total_mass));
+  const double xacc = rsub(temp, rmul(rmul(polemass_length, thetaacc), costheta) / total_mass);
+  x = radd(x, rmul(tau, x_dot));
+  x_dot = radd(x_dot, rmul(tau, xacc));
+  theta = radd(theta, rmul(tau, theta_dot));
+  theta_dot = radd(theta_dot, rmul(tau, thetaacc));
+  s[0] = x, s[1] = x_dot, s[2] = theta, s[3] = theta_dot;
+  return x < -x_threshold || x > x_threshold || theta < -theta_threshold || theta > theta_threshold;
+}
 
 // ------------------------------------------------------------------ Acrobot
 // envs.Acrobot._dsdt (gym 0.17.3 classic_control/acrobot.py, the "book" dynamics): every product
@@ -197,9 +261,8 @@ __device__ __forceinline__ void env_store_obs(float *__restrict__ row, const dou
 }
 
 template <int ENV>
-__global__ __launch_bounds__(256) void k_env_reset(EnvActor ea) {
+__global__ __launch_bounds__(256) void k_env_reset(EnvActor a) {
   constexpr int LD = env_ld(EnvSpec<ENV>::D);
-  const MlpActor &a = ea.m;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.N) return;
   double s[4];
@@ -211,18 +274,17 @@ __global__ __launch_bounds__(256) void k_env_reset(EnvActor ea) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     a.stats[i * 3 + k] = 0;
-    ea.ret_stats[i * 3 + k] = 0.0;
+    if (a.ret_stats) a.ret_stats[i * 3 + k] = 0.0;
   }
   env_store_obs<ENV>(a.obs_ring + (i * a.ring + 1) * LD, s);
   a.cur_slot[i] = 1;
 }
 
 template <int ENV>
-__global__ __launch_bounds__(kMlpThreads) void k_env_actor_step(EnvActor ea) {
+__global__ __launch_bounds__(kMlpThreads) void k_env_actor_step(EnvActor a) {
   constexpr int D = EnvSpec<ENV>::D, A = EnvSpec<ENV>::A, LD = env_ld(D);
   static_assert(D % 2 == 0 && D <= kMlpMaxD && A <= kMlpMaxA, "row_obs moves as 8-byte pieces");
   __shared__ __align__(16) MlpSmem s;
-  const MlpActor &a = ea.m;
   const int tid = threadIdx.x;
   const int64_t N = a.N;
   const int ring = a.ring;
@@ -253,23 +315,26 @@ __global__ __launch_bounds__(kMlpThreads) void k_env_actor_step(EnvActor ea) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) st[k] = a.state[i * 4 + k];
     const int steps = a.ep_steps[i] + 1;
+    // (the running return is fetched with the state: after the ring stores below, which it may
+    // alias for all the compiler knows, its latency would be the lane's own)
+    double *rs = a.ret_stats ? a.ret_stats + i * 3 : nullptr;  // NULL for every lane or for none
+    const double run = rs ? rs[0] : 0.0;
     float rew;
     const bool done = env_dynamics<ENV>(st, act, &rew) | (steps >= a.max_steps);
     const int64_t cur = a.cur_slot[i];
     const int64_t nxt = (2 * t) % ring, rst = (2 * t + 1) % ring;
     const int64_t s0h = i * ring + cur, s1h = i * ring + nxt;
     env_store_obs<ENV>(a.obs_ring + s1h * LD, st);  // the terminal observation when done
-    const double ret = radd(ea.ret_stats[i * 3 + 0], (double)rew);
+    const double ret = radd(run, (double)rew);
     if (done) {
       env_reset_draw<ENV>(a.seed, i, t, st);
       env_store_obs<ENV>(a.obs_ring + (i * ring + rst) * LD, st);
       a.stats[i * 3 + 0] += 1;
       a.stats[i * 3 + 1] += steps;
       a.stats[i * 3 + 2] = steps;
-      ea.ret_stats[i * 3 + 1] = radd(ea.ret_stats[i * 3 + 1], ret);
-      ea.ret_stats[i * 3 + 2] = ret;
+      if (rs) rs[1] = radd(rs[1], ret), rs[2] = ret;
     }
-    ea.ret_stats[i * 3 + 0] = done ? 0.0 : ret;
+    if (rs) rs[0] = done ? 0.0 : ret;
 #pragma unroll
     for (int k = 0; k < 4; ++k) a.state[i * 4 + k] = st[k];
     a.ep_steps[i] = done ? 0 : steps;
@@ -285,10 +350,13 @@ __global__ __launch_bounds__(kMlpThreads) void k_env_actor_step(EnvActor ea) {
     if (a.emit[i]) {  // the emitted row by value: its observations out of the ring, dense [N, D]
       const float2 *o0 = reinterpret_cast<const float2 *>(a.obs_ring + a.row_s0[i] * LD);
       const float2 *o1 = reinterpret_cast<const float2 *>(a.obs_ring + a.row_s1[i] * LD);
+      float2 v0[D / 2], v1[D / 2];  // every piece fetched before the first is stored: one round trip, not D
+#pragma unroll
+      for (int k = 0; k < D / 2; ++k) v0[k] = o0[k], v1[k] = o1[k];
 #pragma unroll
       for (int k = 0; k < D / 2; ++k) {
-        reinterpret_cast<float2 *>(a.row_obs0)[i * (D / 2) + k] = o0[k];
-        reinterpret_cast<float2 *>(a.row_obs1)[i * (D / 2) + k] = o1[k];
+        reinterpret_cast<float2 *>(a.row_obs0)[i * (D / 2) + k] = v0[k];
+        reinterpret_cast<float2 *>(a.row_obs1)[i * (D / 2) + k] = v1[k];
       }
     }
   }
@@ -303,8 +371,10 @@ inline bool env_shape(int64_t env, int *D, int *A) {
   }
 }
 
-// the argument checks of both entry points; `h`: the adder of a step (NULL for the reset)
-inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep *h, bool step, EnvActor *out) {
+// the argument checks of the entry points; `h`: the adder of a step (NULL for the reset);
+// `want_ret`: ret_stats must be there (the CartPole adapters pass none)
+inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep *h, bool step, bool want_ret,
+                                   EnvActor *out) {
   if (!x) return "NULL args";
   int D, A;
   if (!env_shape(x->env, &D, &A)) return "unknown env id (RTH_ENV_CARTPOLE, RTH_ENV_ACROBOT, RTH_ENV_MOUNTAINCAR)";
@@ -314,15 +384,15 @@ inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep 
   if (x->N < 1 || x->N >= (int64_t(1) << 31)) return "bad N (1 <= N < 2^31)";
   if (x->ring < 4) return "bad ring (ring >= 4)";
   if (x->max_episode_steps < 1) return "bad max_episode_steps (>= 1)";
-  if (!x->state || !x->ep_steps || !x->t_dev || !x->stats || !x->ret_stats || !x->obs_ring || !x->cur_slot)
+  if (!x->state || !x->ep_steps || !x->t_dev || !x->stats || (want_ret && !x->ret_stats) || !x->obs_ring ||
+      !x->cur_slot)
     return "NULL state buffer";
-  EnvActor ea{};
-  MlpActor &a = ea.m;
+  EnvActor a{};
   if (step) {
     if (!h) return "NULL adder handle";
     if (x->N != h->N) return "N differs from the adder's";
     if (x->ring < 2 * (h->n + 2)) return "bad ring (ring >= 2 (n_step + 2): an emitted row's observations must survive)";
-    if (!mlp_net(x->params, &a.net)) return "NULL network parameter";
+    if (!dense_net(x->params, &a.net)) return "NULL network parameter";
     if (!x->eps || !x->action || !x->reward || !x->done || !x->s0_h || !x->s1_h || !x->emit || !x->row_s0 ||
         !x->row_a || !x->row_s1 || !x->row_r || !x->row_done || !x->row_obs0 || !x->row_obs1)
       return "NULL step buffer";
@@ -331,15 +401,38 @@ inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep 
     a.ns = h->st, a.n = h->n, a.gamma = h->gamma, a.mode = h->mode;
   }
   if (reinterpret_cast<uintptr_t>(x->obs_ring) & 15) return "obs_ring must be 16-byte aligned";
-  a.state = x->state, a.ep_steps = x->ep_steps, a.t_dev = x->t_dev, a.stats = x->stats;
+  a.state = x->state, a.ep_steps = x->ep_steps, a.t_dev = x->t_dev, a.stats = x->stats, a.ret_stats = x->ret_stats;
   a.obs_ring = x->obs_ring, a.cur_slot = x->cur_slot, a.eps = x->eps, a.action_in = x->action_in;
   a.action = x->action, a.reward = x->reward, a.done = x->done, a.s0_h = x->s0_h, a.s1_h = x->s1_h;
   a.emit = x->emit, a.row_s0 = x->row_s0, a.row_a = x->row_a, a.row_s1 = x->row_s1, a.row_r = x->row_r;
   a.row_done = x->row_done, a.row_obs0 = x->row_obs0, a.row_obs1 = x->row_obs1, a.q_out = x->q_out;
   a.seed = x->seed, a.N = x->N, a.ring = x->ring, a.max_steps = x->max_episode_steps;
-  ea.ret_stats = x->ret_stats;
-  *out = ea;
+  *out = a;
   return nullptr;
+}
+
+template <int ENV>
+inline void env_launch(bool step, const EnvActor &a, hipStream_t st) {
+  if (step)
+    hipLaunchKernelGGL(k_env_actor_step<ENV>, dim3(dense_grid(a.N)), dim3(kMlpThreads), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_env_reset<ENV>, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// The body of the four entry points: the checks, then the env's step (with the adder `h`) or reset
+// kernel.  `fn`: the entry point that was called, for its error messages.
+inline int env_actor_run(const char *fn, const rth_nstep *h, const rth_env_actor_args *x, bool step, bool want_ret,
+                         void *stream) {
+  EnvActor a;
+  const char *bad = env_actor_check(x, h, step, want_ret, &a);
+  RTH_REQUIRE(!bad, "%s: %s", fn, bad);
+  switch (x->env) {
+    case RTH_ENV_CARTPOLE: env_launch<RTH_ENV_CARTPOLE>(step, a, as_stream(stream)); break;
+    case RTH_ENV_ACROBOT: env_launch<RTH_ENV_ACROBOT>(step, a, as_stream(stream)); break;
+    default: env_launch<RTH_ENV_MOUNTAINCAR>(step, a, as_stream(stream));
+  }
+  RTH_LAUNCHED();
+  return RTH_OK;
 }
 
 }  // namespace rth
@@ -347,44 +440,11 @@ inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep 
 extern "C" {
 
 int rth_env_reset(const rth_env_actor_args *args, void *stream) {
-  using namespace rth;
-  EnvActor ea;
-  const char *bad = env_actor_check(args, nullptr, false, &ea);
-  RTH_REQUIRE(!bad, "rth_env_reset: %s", bad);
-  const dim3 grid((unsigned)((ea.m.N + 255) / 256)), block(256);
-  switch (args->env) {
-    case RTH_ENV_CARTPOLE:
-      hipLaunchKernelGGL(k_env_reset<RTH_ENV_CARTPOLE>, grid, block, 0, as_stream(stream), ea);
-      break;
-    case RTH_ENV_ACROBOT:
-      hipLaunchKernelGGL(k_env_reset<RTH_ENV_ACROBOT>, grid, block, 0, as_stream(stream), ea);
-      break;
-    default:
-      hipLaunchKernelGGL(k_env_reset<RTH_ENV_MOUNTAINCAR>, grid, block, 0, as_stream(stream), ea);
-  }
-  RTH_LAUNCHED();
-  return RTH_OK;
+  return rth::env_actor_run("rth_env_reset", nullptr, args, false, true, stream);
 }
 
 int rth_env_actor_step(rth_nstep *h, const rth_env_actor_args *args, void *stream) {
-  using namespace rth;
-  EnvActor ea;
-  const char *bad = env_actor_check(args, h, true, &ea);
-  RTH_REQUIRE(!bad, "rth_env_actor_step: %s", bad);
-  const int64_t tiles = (ea.m.N + kMlpRows - 1) / kMlpRows;
-  const dim3 grid((unsigned)(tiles < kMlpMaxBlocks ? tiles : kMlpMaxBlocks)), block(kMlpThreads);
-  switch (args->env) {
-    case RTH_ENV_CARTPOLE:
-      hipLaunchKernelGGL(k_env_actor_step<RTH_ENV_CARTPOLE>, grid, block, 0, as_stream(stream), ea);
-      break;
-    case RTH_ENV_ACROBOT:
-      hipLaunchKernelGGL(k_env_actor_step<RTH_ENV_ACROBOT>, grid, block, 0, as_stream(stream), ea);
-      break;
-    default:
-      hipLaunchKernelGGL(k_env_actor_step<RTH_ENV_MOUNTAINCAR>, grid, block, 0, as_stream(stream), ea);
-  }
-  RTH_LAUNCHED();
-  return RTH_OK;
+  return rth::env_actor_run("rth_env_actor_step", h, args, true, true, stream);
 }
 
 }  // extern "C"

@@ -7,33 +7,21 @@
 // 128 x 128 middle layer with a row stride of 132 floats: ds_read_b128 down a row and ds_read_b32
 // down a column are both conflict-free) and walks tiles of kMlpRows rows, so a forward's only HBM
 // / L2 round trip is its input rows.  Every product is one fmaf (VALU, one rounding).  A dot
-// product over k has ONE summation order -- mlp_forward_tile is the only forward -- : term k
-// goes to accumulator k % 8 in increasing k, the eight are added as ((0+1)+(2+3))+((4+5)+(6+7)),
+// product over k has ONE summation order -- dense.hpp's; mlp_forward_tile is the only forward --,
 // then the bias: a row's Q does not depend on n, on its position or on the entry point.  The weight
-// and bias gradients sum over the batch in index order (row b to accumulator b % 4, then
-// (0+1)+(2+3)) per output element, whatever the grid: no atomics, identical run to run.
+// and bias gradients and the loss sum over the batch in dense.hpp's order, with its functions.
 #pragma once
-#include "common.hpp"
+#include "dense.hpp"
 
 namespace rth {
 
-constexpr int kMlpH = 128, kMlpMaxD = 64, kMlpMaxA = 18;
-constexpr int kMlpRows = 8;       // rows per tile
-constexpr int kMlpThreads = 256;  // lane j = tid % 128: hidden unit; tid / 128: which 4 of the tile's rows
+constexpr int kMlpH = 128, kMlpMaxD = kDenseMaxD, kMlpMaxA = 18;
+constexpr int kMlpRows = kDenseRows;        // rows per tile
+constexpr int kMlpThreads = kDenseThreads;  // lane j = tid % 128: hidden unit; tid / 128: which 4 of the tile's rows
 constexpr int kMlpRpt = kMlpRows / (kMlpThreads / kMlpH);
 constexpr int kMlpLdw = kMlpH + 4;  // LDS row stride of the staged middle and last layer
 constexpr int kMlpLd1 = kMlpMaxD + 4;  // ... of the first layer (columns [D, round-up-8(D)) zero)
-constexpr int kMlpMaxBlocks = 1024;
-constexpr int kMlpGradThreads = 128, kMlpGradJ = 4;  // second launch: 4 output rows x <= 128 columns per workgroup
 static_assert(kMlpRows * kMlpMaxA <= kMlpThreads && kMlpMaxA <= kMaxActions, "one lane per (row, action)");
-
-struct MlpNet {  // nn.0.weight [H, D], nn.0.bias, nn.2.weight [H, H], nn.2.bias, nn.4.weight [A, H], nn.4.bias
-  const float *w1, *b1, *w2, *b2, *w3, *b3;
-};
-
-struct MlpGrads {
-  float *w1, *b1, *w2, *b2, *w3, *b3;
-};
 
 struct MlpSmem {
   float w2[kMlpH * kMlpLdw];
@@ -64,24 +52,8 @@ struct MlpWs {
   static int64_t floats(int64_t B, int64_t A) { return 2 * B * A + B + 4 * B * kMlpH; }
 };
 
-__device__ __forceinline__ float mlp_relu(float v) { return v < 0.0f ? 0.0f : v; }  // NaN passes, like torch
-__device__ __forceinline__ float mlp_tree8(const float (&a)[8]) {
-  return radd(radd(radd(a[0], a[1]), radd(a[2], a[3])), radd(radd(a[4], a[5]), radd(a[6], a[7])));
-}
-__device__ __forceinline__ void mlp_fma8(const float4 &xa, const float4 &xb, const float4 &wa, const float4 &wb,
-                                         float (&acc)[8]) {
-  acc[0] = fmaf(xa.x, wa.x, acc[0]);
-  acc[1] = fmaf(xa.y, wa.y, acc[1]);
-  acc[2] = fmaf(xa.z, wa.z, acc[2]);
-  acc[3] = fmaf(xa.w, wa.w, acc[3]);
-  acc[4] = fmaf(xb.x, wb.x, acc[4]);
-  acc[5] = fmaf(xb.y, wb.y, acc[5]);
-  acc[6] = fmaf(xb.z, wb.z, acc[6]);
-  acc[7] = fmaf(xb.w, wb.w, acc[7]);
-}
-
 // the network's parameters into LDS; the caller synchronises before they are read
-__device__ inline void mlp_stage_net(const MlpNet &p, int D, int A, MlpSmem &s) {
+__device__ inline void mlp_stage_net(const DenseNet &p, int D, int A, MlpSmem &s) {
   const int tid = threadIdx.x;
   if ((reinterpret_cast<uintptr_t>(p.w2) & 15) == 0) {  // every load of the middle layer in flight at once
     constexpr int N4 = kMlpH * kMlpH / 4 / kMlpThreads;
@@ -113,17 +85,7 @@ __device__ inline void mlp_stage_net(const MlpNet &p, int D, int A, MlpSmem &s) 
   if (tid < A) s.b3[tid] = p.b3[tid];
 }
 
-// rows [r0, r0 + kMlpRows) of x [n, D] (row stride ldx) into xs, zero past n and past D: nothing
-// outside [0, n) x [0, D) is read.  No barrier.
-__device__ inline void mlp_load_x(const float *__restrict__ x, int64_t ldx, int64_t n, int64_t r0, int D,
-                                  float (*xs)[kMlpMaxD]) {
-  for (int i = threadIdx.x; i < kMlpRows * kMlpMaxD; i += kMlpThreads) {
-    const int r = i / kMlpMaxD, k = i % kMlpMaxD;
-    xs[r][k] = (r0 + r < n && k < D) ? x[(r0 + r) * ldx + k] : 0.0f;
-  }
-}
-
-// The forward of the kMlpRows rows in xs (mlp_load_x) through the net staged in s (mlp_stage_net):
+// The forward of the kMlpRows rows in xs (dense_load_x) through the net staged in s (mlp_stage_net):
 // s.h1 / s.h2 = the hidden activations, s.q = Q.  Starts and ends with a workgroup barrier.
 __device__ inline void mlp_forward_rows(const float (*xs)[kMlpMaxD], int D, int A, MlpSmem &s) {
   const int tid = threadIdx.x, j = tid & (kMlpH - 1), rb = (tid >> 7) * kMlpRpt;
@@ -138,12 +100,12 @@ __device__ inline void mlp_forward_rows(const float (*xs)[kMlpMaxD], int D, int 
       for (int rr = 0; rr < kMlpRpt; ++rr) {
         const float4 xa = *reinterpret_cast<const float4 *>(&xs[rb + rr][k0]);
         const float4 xb = *reinterpret_cast<const float4 *>(&xs[rb + rr][k0 + 4]);
-        mlp_fma8(xa, xb, wa, wb, acc[rr]);
+        dense_fma8(xa, xb, wa, wb, acc[rr]);
       }
     }
     const float b = s.b1[j];
 #pragma unroll
-    for (int rr = 0; rr < kMlpRpt; ++rr) s.h1[rb + rr][j] = mlp_relu(radd(mlp_tree8(acc[rr]), b));
+    for (int rr = 0; rr < kMlpRpt; ++rr) s.h1[rb + rr][j] = dense_relu(radd(dense_tree8(acc[rr]), b));
   }
   __syncthreads();
   {  // layer 2 from LDS
@@ -157,12 +119,12 @@ __device__ inline void mlp_forward_rows(const float (*xs)[kMlpMaxD], int D, int 
       for (int rr = 0; rr < kMlpRpt; ++rr) {
         const float4 xa = *reinterpret_cast<const float4 *>(&s.h1[rb + rr][k0]);
         const float4 xb = *reinterpret_cast<const float4 *>(&s.h1[rb + rr][k0 + 4]);
-        mlp_fma8(xa, xb, wa, wb, acc[rr]);
+        dense_fma8(xa, xb, wa, wb, acc[rr]);
       }
     }
     const float b = s.b2[j];
 #pragma unroll
-    for (int rr = 0; rr < kMlpRpt; ++rr) s.h2[rb + rr][j] = mlp_relu(radd(mlp_tree8(acc[rr]), b));
+    for (int rr = 0; rr < kMlpRpt; ++rr) s.h2[rb + rr][j] = dense_relu(radd(dense_tree8(acc[rr]), b));
   }
   __syncthreads();
   if (tid < kMlpRows * A) {  // layer 3: one lane per (row, action)
@@ -175,18 +137,18 @@ __device__ inline void mlp_forward_rows(const float (*xs)[kMlpMaxD], int D, int 
       const float4 wb = *reinterpret_cast<const float4 *>(w + k0 + 4);
       const float4 xa = *reinterpret_cast<const float4 *>(&s.h2[r][k0]);
       const float4 xb = *reinterpret_cast<const float4 *>(&s.h2[r][k0 + 4]);
-      mlp_fma8(xa, xb, wa, wb, acc);
+      dense_fma8(xa, xb, wa, wb, acc);
     }
-    s.q[r][a] = radd(mlp_tree8(acc), s.b3[a]);
+    s.q[r][a] = radd(dense_tree8(acc), s.b3[a]);
   }
   __syncthreads();
 }
 
-// mlp_load_x into s.x behind a barrier (the previous tile is done with s), then the forward
+// dense_load_x into s.x behind a barrier (the previous tile is done with s), then the forward
 __device__ inline void mlp_forward_tile(const float *__restrict__ x, int64_t ldx, int64_t n, int64_t r0, int D, int A,
                                         MlpSmem &s) {
   __syncthreads();
-  mlp_load_x(x, ldx, n, r0, D, s.x);
+  dense_load_x(x, ldx, n, r0, D, s.x);
   mlp_forward_rows(s.x, D, A, s);
 }
 
@@ -199,7 +161,7 @@ __device__ inline void mlp_store_q(const MlpSmem &s, float *__restrict__ q, int6
   }
 }
 
-__global__ __launch_bounds__(kMlpThreads) void k_mlp_q(MlpNet p, const float *__restrict__ x, int64_t ldx, int64_t n,
+__global__ __launch_bounds__(kMlpThreads) void k_mlp_q(DenseNet p, const float *__restrict__ x, int64_t ldx, int64_t n,
                                                        int D, int A, float *__restrict__ q,
                                                        int32_t *__restrict__ amax) {
   __shared__ __align__(16) MlpSmem s;
@@ -221,7 +183,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_q(MlpNet p, const float *__
 // data gradients of the online net's three layers; the activations and pre-activation gradients
 // go to the workspace for the second launch, stored at the tile's end (no barrier waits on them).
 __global__ __launch_bounds__(kMlpThreads) void k_mlp_td(
-    MlpNet on, MlpNet tg, const float *__restrict__ s0, int64_t lds0, const float *__restrict__ s1, int64_t lds1,
+    DenseNet on, DenseNet tg, const float *__restrict__ s0, int64_t lds0, const float *__restrict__ s1, int64_t lds1,
     const int64_t *__restrict__ act, const float *__restrict__ rew, const float *__restrict__ done,
     const double *__restrict__ isw, int64_t B, int D, int A, float gamma_n, int double_q, int backward,
     float *__restrict__ wsp, float *__restrict__ td_abs) {
@@ -242,8 +204,8 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_td(
     const bool qlane = tid < kMlpRows * A;  // lane (r, a) = tid of the tile's Q row blocks
     const int qr = tid / A, qa = tid % A;
     __syncthreads();
-    mlp_load_x(s0, lds0, B, r0, D, s.x);
-    if (double_q) mlp_load_x(s1, lds1, B, r0, D, s.x1);
+    dense_load_x(s0, lds0, B, r0, D, s.x);
+    if (double_q) dense_load_x(s1, lds1, B, r0, D, s.x1);
     if (qlane) s.tq1t[tid] = r0 + qr < B ? ws.q1t[(r0 + qr) * A + qa] : 0.0f;  // written by this workgroup above
     if (tid >= kMlpH && tid < kMlpH + kMlpRows && r0 + (tid - kMlpH) < B) {
       const int r = tid - kMlpH;
@@ -293,7 +255,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_td(
         for (int rr = 0; rr < kMlpRpt; ++rr) {
           const float4 ga = *reinterpret_cast<const float4 *>(&s.g2[rb + rr][j0]);
           const float4 gb = *reinterpret_cast<const float4 *>(&s.g2[rb + rr][j0 + 4]);
-          mlp_fma8(ga, gb, wa, wb, acc[rr]);
+          dense_fma8(ga, gb, wa, wb, acc[rr]);
         }
       }
 #pragma unroll
@@ -301,7 +263,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_td(
         const int r = rb + rr;
         if (r0 + r < B) {
           const int64_t o = (r0 + r) * kMlpH + j;
-          ws.g1[o] = s.h1[r][j] > 0.0f ? mlp_tree8(acc[rr]) : 0.0f;
+          ws.g1[o] = s.h1[r][j] > 0.0f ? dense_tree8(acc[rr]) : 0.0f;
           ws.g2[o] = s.g2[r][j];
           ws.h2[o] = s.h2[r][j];
           ws.h1[o] = s.h1[r][j];
@@ -312,97 +274,33 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_td(
   }
 }
 
-// gw[n][k] = sum_b G[b][n] X[b][k] for the rows n in [n0, n0 + kMlpGradJ) of one layer: lane k, row b
-// to accumulator b % 4
-__device__ inline void mlp_wgrad_tile(const float *__restrict__ G, int64_t ldg, int N, const float *__restrict__ X,
-                                      int64_t ldx, int K, int64_t B, int n0, float *__restrict__ gw) {
-  const int k = threadIdx.x;
-  if (k >= K) return;
-  float acc[kMlpGradJ][4] = {};
-  int nn[kMlpGradJ];
-#pragma unroll
-  for (int i = 0; i < kMlpGradJ; ++i) nn[i] = n0 + i < N ? n0 + i : N - 1;  // clamped: read in bounds, not stored
-  int64_t b = 0;
-#pragma unroll 4
-  for (; b + 4 <= B; b += 4) {  // (unrolled: 16 rows' loads in flight; the order of the sums is unchanged)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float x = X[(b + u) * ldx + k];
-#pragma unroll
-      for (int i = 0; i < kMlpGradJ; ++i) acc[i][u] = fmaf(G[(b + u) * ldg + nn[i]], x, acc[i][u]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    if (b + u < B) {
-      const float x = X[(b + u) * ldx + k];
-#pragma unroll
-      for (int i = 0; i < kMlpGradJ; ++i) acc[i][u] = fmaf(G[(b + u) * ldg + nn[i]], x, acc[i][u]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < kMlpGradJ; ++i)
-    if (n0 + i < N) gw[(int64_t)(n0 + i) * K + k] = radd(radd(acc[i][0], acc[i][1]), radd(acc[i][2], acc[i][3]));
-}
-
-// gb[n] = sum_b G[b][n], lane n, the same order over b
-__device__ inline void mlp_bgrad(const float *__restrict__ G, int64_t ldg, int N, int64_t B, float *__restrict__ gb) {
-  const int n = threadIdx.x;
-  if (n >= N) return;
-  float acc[4] = {};
-  int64_t b = 0;
-#pragma unroll 4
-  for (; b + 4 <= B; b += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = radd(acc[u], G[(b + u) * ldg + n]);
-  }
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-    if (b + u < B) acc[u] = radd(acc[u], G[(b + u) * ldg + n]);
-  gb[n] = radd(radd(acc[0], acc[1]), radd(acc[2], acc[3]));
-}
-
 // rth_mlp_dqn_grads' second launch: workgroups [0, 32) the middle layer's weight gradient, [32, 64)
 // the first layer's, then ceil(A / 4) for the last layer's, three for the bias gradients and the
 // last one the loss mean (k_td_huber's per-lane sums and LDS tree); without gradients only the mean
-__global__ __launch_bounds__(kMlpGradThreads) void k_mlp_wgrad(MlpGrads g, const float *__restrict__ s0, int64_t lds0,
-                                                               int64_t B, int D, int A, float *__restrict__ wsp,
-                                                               float *__restrict__ loss, int first) {
-  __shared__ float part[kMlpGradThreads];
+__global__ __launch_bounds__(kDenseGradThreads) void k_mlp_wgrad(DenseGrads g, const float *__restrict__ s0,
+                                                                 int64_t lds0, int64_t B, int D, int A,
+                                                                 float *__restrict__ wsp, float *__restrict__ loss,
+                                                                 int first) {
+  __shared__ float part[kDenseGradThreads];
   const MlpWs ws(wsp, B, A);
-  constexpr int T = kMlpH / kMlpGradJ;
-  const int a_tiles = (A + kMlpGradJ - 1) / kMlpGradJ;
+  constexpr int T = kMlpH / kDenseGradJ;
+  const int a_tiles = (A + kDenseGradJ - 1) / kDenseGradJ;
   int blk = (int)blockIdx.x + first;
-  if (blk < T) return mlp_wgrad_tile(ws.g2, kMlpH, kMlpH, ws.h1, kMlpH, kMlpH, B, blk * kMlpGradJ, g.w2);
+  if (blk < T) return dense_wgrad_tile(ws.g2, kMlpH, kMlpH, ws.h1, kMlpH, kMlpH, B, blk * kDenseGradJ, 0, g.w2);
   blk -= T;
-  if (blk < T) return mlp_wgrad_tile(ws.g1, kMlpH, kMlpH, s0, lds0, D, B, blk * kMlpGradJ, g.w1);
+  if (blk < T) return dense_wgrad_tile(ws.g1, kMlpH, kMlpH, s0, lds0, D, B, blk * kDenseGradJ, 0, g.w1);
   blk -= T;
-  if (blk < a_tiles) return mlp_wgrad_tile(ws.g3, A, A, ws.h2, kMlpH, kMlpH, B, blk * kMlpGradJ, g.w3);
+  if (blk < a_tiles) return dense_wgrad_tile(ws.g3, A, A, ws.h2, kMlpH, kMlpH, B, blk * kDenseGradJ, 0, g.w3);
   blk -= a_tiles;
-  if (blk == 0) return mlp_bgrad(ws.g1, kMlpH, kMlpH, B, g.b1);
-  if (blk == 1) return mlp_bgrad(ws.g2, kMlpH, kMlpH, B, g.b2);
-  if (blk == 2) return mlp_bgrad(ws.g3, A, A, B, g.b3);
-  float acc = 0.0f;
-  for (int64_t b = threadIdx.x; b < B; b += kMlpGradThreads) acc = radd(acc, ws.le[b]);
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int st = kMlpGradThreads / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) part[threadIdx.x] = radd(part[threadIdx.x], part[threadIdx.x + st]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) loss[0] = part[0] * (1.0f / (float)B);
+  if (blk == 0) return dense_bgrad(ws.g1, kMlpH, kMlpH, B, 0, g.b1);
+  if (blk == 1) return dense_bgrad(ws.g2, kMlpH, kMlpH, B, 0, g.b2);
+  if (blk == 2) return dense_bgrad(ws.g3, A, A, B, 0, g.b3);
+  const float sum = dense_loss_sum(ws.le, B, part);
+  if (threadIdx.x == 0 && loss) loss[0] = sum * (1.0f / (float)B);
 }
 
 inline bool mlp_shape_ok(int64_t D, int64_t H, int64_t A) {
   return H == kMlpH && D >= 1 && D <= kMlpMaxD && A >= 1 && A <= kMlpMaxA;
-}
-
-inline bool mlp_net(const float *const *params, MlpNet *out) {
-  if (!params) return false;
-  for (int i = 0; i < 6; ++i)
-    if (!params[i]) return false;
-  *out = MlpNet{params[0], params[1], params[2], params[3], params[4], params[5]};
-  return true;
 }
 
 }  // namespace rth
@@ -426,11 +324,10 @@ int rth_mlp_q(const float *const *params, const float *x_dev, int64_t ldx, int64
               (long long)D, (long long)H, (long long)A);
   RTH_REQUIRE(n >= 1 && ldx >= D, "rth_mlp_q: bad n=%lld or ldx=%lld < D=%lld", (long long)n, (long long)ldx,
               (long long)D);
-  MlpNet p;
-  RTH_REQUIRE(mlp_net(params, &p) && x_dev && q_dev, "rth_mlp_q: NULL argument");
-  const int64_t tiles = (n + kMlpRows - 1) / kMlpRows;
-  hipLaunchKernelGGL(k_mlp_q, dim3((unsigned)(tiles < kMlpMaxBlocks ? tiles : kMlpMaxBlocks)), dim3(kMlpThreads), 0,
-                     as_stream(stream), p, x_dev, ldx, n, (int)D, (int)A, q_dev, argmax_dev);
+  DenseNet p;
+  RTH_REQUIRE(dense_net(params, &p) && x_dev && q_dev, "rth_mlp_q: NULL argument");
+  hipLaunchKernelGGL(k_mlp_q, dim3(dense_grid(n)), dim3(kMlpThreads), 0, as_stream(stream), p, x_dev, ldx, n, (int)D,
+                     (int)A, q_dev, argmax_dev);
   RTH_LAUNCHED();
   return RTH_OK;
 }
@@ -447,28 +344,27 @@ int rth_mlp_dqn_grads(const float *const *online, const float *const *target, co
   RTH_REQUIRE(B >= 1 && B <= (int64_t)1 << 40 && lds0 >= D && lds1 >= D,
               "rth_mlp_dqn_grads: bad B=%lld or row stride (%lld, %lld) < D=%lld", (long long)B, (long long)lds0,
               (long long)lds1, (long long)D);
-  MlpNet on, tg;
-  RTH_REQUIRE(mlp_net(online, &on) && mlp_net(target, &tg) && s0_dev && s1_dev && a_dev && r_dev && done_dev &&
+  DenseNet on, tg;
+  RTH_REQUIRE(dense_net(online, &on) && dense_net(target, &tg) && s0_dev && s1_dev && a_dev && r_dev && done_dev &&
                   workspace_dev,
               "rth_mlp_dqn_grads: NULL argument");
-  MlpGrads g{};
+  DenseGrads g{};
   if (grads) {
     for (int i = 0; i < 6; ++i) RTH_REQUIRE(grads[i], "rth_mlp_dqn_grads: NULL gradient buffer %d", i);
-    g = MlpGrads{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
+    g = DenseGrads{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]};
   }
   float *ws = static_cast<float *>(workspace_dev);
-  const int64_t tiles = (B + kMlpRows - 1) / kMlpRows;
-  hipLaunchKernelGGL(k_mlp_td, dim3((unsigned)(tiles < kMlpMaxBlocks ? tiles : kMlpMaxBlocks)), dim3(kMlpThreads), 0,
-                     as_stream(stream), on, tg, s0_dev, lds0, s1_dev, lds1, a_dev, r_dev, done_dev, isw_dev, B, (int)D,
-                     (int)A, gamma_n, (int)(double_q != 0), (int)(grads != nullptr), ws, td_abs_dev);
+  hipLaunchKernelGGL(k_mlp_td, dim3(dense_grid(B)), dim3(kMlpThreads), 0, as_stream(stream), on, tg, s0_dev, lds0,
+                     s1_dev, lds1, a_dev, r_dev, done_dev, isw_dev, B, (int)D, (int)A, gamma_n, (int)(double_q != 0),
+                     (int)(grads != nullptr), ws, td_abs_dev);
   RTH_LAUNCHED();
-  const int grad_blocks = 2 * (kMlpH / kMlpGradJ) + (int)((A + kMlpGradJ - 1) / kMlpGradJ) + 3;
+  const int grad_blocks = 2 * (kMlpH / kDenseGradJ) + (int)((A + kDenseGradJ - 1) / kDenseGradJ) + 3;
   if (grads) {  // every gradient element, then the loss mean
-    hipLaunchKernelGGL(k_mlp_wgrad, dim3(grad_blocks + 1), dim3(kMlpGradThreads), 0, as_stream(stream), g, s0_dev, lds0,
+    hipLaunchKernelGGL(k_mlp_wgrad, dim3(grad_blocks + 1), dim3(kDenseGradThreads), 0, as_stream(stream), g, s0_dev, lds0,
                        B, (int)D, (int)A, ws, loss_dev, 0);
     RTH_LAUNCHED();
   } else if (loss_dev) {
-    hipLaunchKernelGGL(k_mlp_wgrad, dim3(1), dim3(kMlpGradThreads), 0, as_stream(stream), g, s0_dev, lds0, B, (int)D,
+    hipLaunchKernelGGL(k_mlp_wgrad, dim3(1), dim3(kDenseGradThreads), 0, as_stream(stream), g, s0_dev, lds0, B, (int)D,
                        (int)A, ws, loss_dev, grad_blocks);
     RTH_LAUNCHED();
   }

@@ -1,19 +1,21 @@
-"""Vectorised CartPole actors on one GPU, on the fused MLP kernels (csrc/mlp_actor.hpp).
+"""Vectorised classic-control actors on one GPU, on the fused MLP kernels (csrc/env_actor.hpp).
 
 Reference actor loop: reth/reth/presets/worker.py:128-155 (Worker.step: exploration.act ->
 solver.act, env.step, env.reset on done) and utils/nstep_adder.py:11-28, one host env and one
-transition at a time.  Here N gym CartPole-v0/v1 environments (the dynamics of envs.CartPole, fp64) live in HBM
-and step together in ONE launch per env step (rth_mlp_actor_step): the acting forward of the MLP
-Q-network (bit-equal to rth_mlp_q), ε-greedy with rth_eps_greedy's Philox draws, the dynamics,
-the reset of finished episodes, the f32 observations into a per-env ring and the n-step push.
-Emitted n-step rows come out as ring handles and by value (row_obs0 / row_obs1 [N, 4]), so
+transition at a time.  Here N environments of one kind -- gym's CartPole-v0/v1, Acrobot-v1 or
+MountainCar-v0, the dynamics of envs.py's host classes in fp64 -- live in HBM and step together in
+ONE launch per env step: the acting forward of the MLP Q-network at the env's shape (bit-equal to
+rth_mlp_q), ε-greedy with rth_eps_greedy's Philox draws, the dynamics, the reset of finished
+episodes, the f32 observations into a per-env ring and the n-step push.  Emitted n-step rows come
+out as ring handles and by value (row_obs0 / row_obs1 [N, obs_dim]), so
 DQNSolver.calc_loss_device and HbmReplay.append consume them as dense tensors.  No host
 synchronisation anywhere; every per-step scalar is device-resident, so a captured step replays.
 
 The counterpart of actors.VecActors (conv observations) for 1-D observations.
 
-VecMlpActors is the same actor set for the classic-control family of csrc/env_actor.hpp
-(rth_env_actor_step: CartPole, Acrobot-v1, MountainCar-v0), each env at its own network shape.
+VecMlpActors(env, n, ...) is the implementation, on rth_env_reset / rth_env_actor_step.
+VecCartPoleActors(n, ...) is the same set fixed to CartPole-v0 through the CartPole entry points
+(rth_cartpole_reset / rth_mlp_actor_step: adapters onto the same kernel, without return statistics).
 """
 import numpy as np
 import torch
@@ -22,22 +24,43 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .actors import apex_epsilons
 
-OBS_DIM, NUM_ACTIONS = 4, 2
+OBS_DIM, NUM_ACTIONS = 4, 2  # CartPole's
+
+# env name -> (RTH_ENV_* id, obs_dim, num_actions, TimeLimit) of the classic-control family (csrc/env_actor.hpp)
+ENVS = {"CartPole-v0": (_lib.ENV_CARTPOLE, 4, 2, 200), "CartPole-v1": (_lib.ENV_CARTPOLE, 4, 2, 500),
+        "Acrobot-v1": (_lib.ENV_ACROBOT, 6, 3, 500), "MountainCar-v0": (_lib.ENV_MOUNTAINCAR, 2, 3, 200)}
 
 
-class VecCartPoleActors:
-    name = "CartPole"
-    obs_dim, num_actions = OBS_DIM, NUM_ACTIONS
-    ld = 4  # the ring's row stride in floats
-    _reset_fn, _step_fn = "rth_cartpole_reset", "rth_mlp_actor_step"
+def row_columns(obs_dim):
+    """replay columns of the rows [s0, a, r, s1, done], cast f4 / i8 / f4 / f4 / f4 as
+    test/apex-dqn/worker.py:47-51 casts them"""
+    from .replay import Column
 
-    def __init__(self, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=200, nstep_mode=0,
+    return [Column((obs_dim,), torch.float32), Column((), torch.int64), Column((), torch.float32),
+            Column((obs_dim,), torch.float32), Column((), torch.float32)]
+
+
+class VecMlpActors:
+    """N envs of `env` (a key of ENVS) stepped by one launch at the env's network shape
+    (obs_dim, 128, num_actions), with the env's reward, terminal rule and observation map.  The
+    ring's rows are obs_dim rounded up to 4 floats (the pad stays 0); rows() are dense
+    [N, obs_dim].  Episode statistics in int64 (episode_stats) and fp64 returns (return_stats).
+    max_episode_steps defaults to the env's TimeLimit."""
+    _reset_fn, _step_fn = "rth_env_reset", "rth_env_actor_step"
+    _keeps_returns = True
+
+    def __init__(self, env, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=None, nstep_mode=0,
                  device=None):
+        if env not in ENVS:
+            raise ValueError(f"VecMlpActors: unknown env {env!r} (device envs: {', '.join(ENVS)})")
+        self.env = self.name = env
+        self.env_id, self.obs_dim, self.num_actions, limit = ENVS[env]
+        self.ld = (self.obs_dim + 3) // 4 * 4  # the ring's row stride in floats
         self.N = int(n_actors)
         self.n_step, self.gamma = int(n_step), float(gamma)
         self.gamma_n = float(np.float32(gamma ** n_step))
         self.seed = int(seed)
-        self.max_episode_steps = int(max_episode_steps)
+        self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
         if self.N < 1 or self.n_step < 1 or self.max_episode_steps < 1:
             raise ValueError("n_actors, n_step and max_episode_steps must be >= 1")
         self.device = torch.device(device if device is not None else "cuda")
@@ -51,7 +74,8 @@ class VecCartPoleActors:
         self.ep_steps = z((N,), torch.int32)
         self.t_dev = z((N,), torch.int64)          # env steps taken, one equal copy per env (the Philox counter)
         self.stats = z((N, 3), torch.int64)        # finished episodes, sum of their lengths, last length
-        self._alloc_more()
+        # running return, sum of the finished episodes' returns, last finished return
+        self.ret_stats = z((N, 3), torch.float64) if self._keeps_returns else None
         self.obs_ring = z((N * ring + 1, self.ld), torch.float32)  # zero-filled once; last row: the sink
         self.cur_slot = z((N,), torch.int64)
         e = apex_epsilons(N) if eps is None else np.array(np.broadcast_to(np.asarray(eps, np.float64), (N,)))
@@ -80,9 +104,6 @@ class VecCartPoleActors:
         """a zero-filled device buffer (tests override it to surround every buffer with guards)"""
         return torch.zeros(shape, dtype=dtype, device=self.device)
 
-    def _alloc_more(self):
-        """a subclass's further state buffers"""
-
     def __del__(self):
         if getattr(self, "_nstep", None):
             try:
@@ -105,13 +126,13 @@ class VecCartPoleActors:
         return self._params_arr
 
     def _args(self, params=None, action_in=None):
-        return _lib.MlpActorArgs(params, OBS_DIM, 128, NUM_ACTIONS, ptr(self.state), ptr(self.ep_steps),
-                                 ptr(self.t_dev), ptr(self.stats), ptr(self.obs_ring), ptr(self.cur_slot),
-                                 ptr(self.eps), ptr(action_in), ptr(self.action), ptr(self.reward), ptr(self.done),
-                                 ptr(self.s0_h), ptr(self.s1_h), ptr(self.emit), ptr(self.row_s0), ptr(self.row_a),
-                                 ptr(self.row_s1), ptr(self.row_r), ptr(self.row_done), ptr(self.row_obs0),
-                                 ptr(self.row_obs1), ptr(self.q_out), self.seed, self.N, self.ring,
-                                 self.max_episode_steps)
+        return _lib.EnvActorArgs(params, self.env_id, self.obs_dim, 128, self.num_actions, ptr(self.state),
+                                 ptr(self.ep_steps), ptr(self.t_dev), ptr(self.stats), ptr(self.ret_stats),
+                                 ptr(self.obs_ring), ptr(self.cur_slot), ptr(self.eps), ptr(action_in),
+                                 ptr(self.action), ptr(self.reward), ptr(self.done), ptr(self.s0_h), ptr(self.s1_h),
+                                 ptr(self.emit), ptr(self.row_s0), ptr(self.row_a), ptr(self.row_s1), ptr(self.row_r),
+                                 ptr(self.row_done), ptr(self.row_obs0), ptr(self.row_obs1), ptr(self.q_out),
+                                 self.seed, self.N, self.ring, self.max_episode_steps)
 
     # ------------------------------------------------------------------ env
     def reset(self):
@@ -128,20 +149,34 @@ class VecCartPoleActors:
         self.q_out = self._alloc((self.N, self.num_actions), torch.float32) if on else None
         return self.q_out
 
+    def observe(self, state):
+        """the env's f32 observation [N, ld] (pad 0) of fp64 states [N, 4], computed by torch"""
+        obs = torch.zeros((state.shape[0], self.ld), dtype=torch.float32, device=state.device)
+        if self.env_id == _lib.ENV_ACROBOT:
+            t = state[:, :2]
+            obs[:, 0:4:2], obs[:, 1:4:2] = torch.cos(t).float(), torch.sin(t).float()
+            obs[:, 4:6] = state[:, 2:4].float()
+        else:
+            obs[:, :self.obs_dim] = state[:, :self.obs_dim].float()
+        return obs
+
     @torch.no_grad()
     def set_state(self, states, steps=None):
-        """inject env states [N, 4] (float64) and, optionally, the running episodes' step counts
-        [N]; the observations the envs act on next become float32(states) (tests)"""
+        """inject env states [N, 4] (float64; [N, k] fills the first k columns) and, optionally, the
+        running episodes' step counts [N]; the observations the envs act on next become those of
+        the states (tests)"""
         st = torch.as_tensor(np.asarray(states, np.float64) if not torch.is_tensor(states) else states)
-        self.state.copy_(st.to(self.device, torch.float64).reshape(self.N, 4))
+        st = st.to(self.device, torch.float64).reshape(self.N, -1)
+        self.state.zero_()
+        self.state[:, :st.shape[1]] = st
         if steps is not None:
             sp = torch.as_tensor(np.asarray(steps) if not torch.is_tensor(steps) else steps)
             self.ep_steps.copy_(sp.to(self.device, torch.int32).reshape(self.N))
-        self.obs_ring[self._base + self.cur_slot] = self.state.to(torch.float32)
+        self.obs_ring[self._base + self.cur_slot] = self.observe(self.state)
 
     def current_obs(self):
-        """the observations [N, 4] the envs act on next (a copy)"""
-        return self.obs_ring[self._base + self.cur_slot]
+        """the observations [N, obs_dim] the envs act on next (a dense copy)"""
+        return self.obs_ring[self._base + self.cur_slot][:, :self.obs_dim].contiguous()
 
     @property
     def warm(self):
@@ -179,83 +214,6 @@ class VecCartPoleActors:
         the last finished length"""
         return self.stats[:, 0], self.stats[:, 1], self.stats[:, 2]
 
-    @staticmethod
-    def columns(obs_dim=OBS_DIM):
-        """replay columns of the rows [s0, a, r, s1, done], cast f4 / i8 / f4 / f4 / f4 as
-        test/apex-dqn/worker.py:47-51 casts them"""
-        from .replay import Column
-
-        return [Column((obs_dim,), torch.float32), Column((), torch.int64), Column((), torch.float32),
-                Column((obs_dim,), torch.float32), Column((), torch.float32)]
-
-
-# env name -> (RTH_ENV_* id, obs_dim, num_actions, TimeLimit) of the classic-control family (csrc/env_actor.hpp)
-ENVS = {"CartPole-v0": (_lib.ENV_CARTPOLE, 4, 2, 200), "CartPole-v1": (_lib.ENV_CARTPOLE, 4, 2, 500),
-        "Acrobot-v1": (_lib.ENV_ACROBOT, 6, 3, 500), "MountainCar-v0": (_lib.ENV_MOUNTAINCAR, 2, 3, 200)}
-
-
-class VecMlpActors(VecCartPoleActors):
-    """VecCartPoleActors for the classic-control family: N envs of `env` (a key of ENVS: the host
-    classes of envs.py, fp64) stepped by one launch of rth_env_actor_step at the env's network
-    shape (obs_dim, 128, num_actions), with the env's reward, terminal rule and observation map.
-    The ring's rows are obs_dim rounded up to 4 floats (the pad stays 0); rows() are dense
-    [N, obs_dim].  Adds fp64 return statistics (return_stats).  max_episode_steps defaults to the
-    env's TimeLimit.  With a CartPole name it computes what VecCartPoleActors computes, bit for
-    bit, through the generic entry point."""
-    _reset_fn, _step_fn = "rth_env_reset", "rth_env_actor_step"
-
-    def __init__(self, env, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=None, nstep_mode=0,
-                 device=None):
-        if env not in ENVS:
-            raise ValueError(f"VecMlpActors: unknown env {env!r} (device envs: {', '.join(ENVS)})")
-        self.env = self.name = env
-        self.env_id, self.obs_dim, self.num_actions, limit = ENVS[env]
-        self.ld = (self.obs_dim + 3) // 4 * 4
-        super().__init__(n_actors, n_step, gamma, eps, seed, limit if max_episode_steps is None else max_episode_steps,
-                         nstep_mode, device)
-
-    def _alloc_more(self):
-        # running return, sum of the finished episodes' returns, last finished return
-        self.ret_stats = self._alloc((self.N, 3), torch.float64)
-
-    def _args(self, params=None, action_in=None):
-        return _lib.EnvActorArgs(params, self.env_id, self.obs_dim, 128, self.num_actions, ptr(self.state),
-                                 ptr(self.ep_steps), ptr(self.t_dev), ptr(self.stats), ptr(self.ret_stats),
-                                 ptr(self.obs_ring), ptr(self.cur_slot), ptr(self.eps), ptr(action_in),
-                                 ptr(self.action), ptr(self.reward), ptr(self.done), ptr(self.s0_h), ptr(self.s1_h),
-                                 ptr(self.emit), ptr(self.row_s0), ptr(self.row_a), ptr(self.row_s1), ptr(self.row_r),
-                                 ptr(self.row_done), ptr(self.row_obs0), ptr(self.row_obs1), ptr(self.q_out),
-                                 self.seed, self.N, self.ring, self.max_episode_steps)
-
-    def observe(self, state):
-        """the env's f32 observation [N, ld] (pad 0) of fp64 states [N, 4], computed by torch"""
-        obs = torch.zeros((state.shape[0], self.ld), dtype=torch.float32, device=state.device)
-        if self.env_id == _lib.ENV_ACROBOT:
-            t = state[:, :2]
-            obs[:, 0:4:2], obs[:, 1:4:2] = torch.cos(t).float(), torch.sin(t).float()
-            obs[:, 4:6] = state[:, 2:4].float()
-        else:
-            obs[:, :self.obs_dim] = state[:, :self.obs_dim].float()
-        return obs
-
-    @torch.no_grad()
-    def set_state(self, states, steps=None):
-        """inject env states [N, 4] (float64; [N, k] fills the first k columns) and, optionally, the
-        running episodes' step counts [N]; the observations the envs act on next become those of
-        the states (tests)"""
-        st = torch.as_tensor(np.asarray(states, np.float64) if not torch.is_tensor(states) else states)
-        st = st.to(self.device, torch.float64).reshape(self.N, -1)
-        self.state.zero_()
-        self.state[:, :st.shape[1]] = st
-        if steps is not None:
-            sp = torch.as_tensor(np.asarray(steps) if not torch.is_tensor(steps) else steps)
-            self.ep_steps.copy_(sp.to(self.device, torch.int32).reshape(self.N))
-        self.obs_ring[self._base + self.cur_slot] = self.observe(self.state)
-
-    def current_obs(self):
-        """the observations [N, obs_dim] the envs act on next (a dense copy)"""
-        return self.obs_ring[self._base + self.cur_slot][:, :self.obs_dim].contiguous()
-
     def return_stats(self):
         """per-env device statistics (float64 [N] each): the running episode's return, the sum of
         the finished episodes' returns, the last finished return"""
@@ -263,4 +221,29 @@ class VecMlpActors(VecCartPoleActors):
 
     def columns(self):
         """replay columns of the rows [s0, a, r, s1, done] at this env's obs_dim"""
-        return VecCartPoleActors.columns(self.obs_dim)
+        return row_columns(self.obs_dim)
+
+
+class VecCartPoleActors(VecMlpActors):
+    """VecMlpActors("CartPole-v0", ...) through rth_cartpole_reset / rth_mlp_actor_step: the same
+    kernel, the same bits, no return statistics (a CartPole return is its length: episode_stats)."""
+    obs_dim, num_actions = OBS_DIM, NUM_ACTIONS
+    _reset_fn, _step_fn = "rth_cartpole_reset", "rth_mlp_actor_step"
+    _keeps_returns = False
+
+    def __init__(self, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=200, nstep_mode=0,
+                 device=None):
+        super().__init__("CartPole-v0", n_actors, n_step, gamma, eps, seed, max_episode_steps, nstep_mode, device)
+
+    def _args(self, params=None, action_in=None):  # rth_env_actor_args without env and ret_stats
+        return _lib.MlpActorArgs(params, OBS_DIM, 128, NUM_ACTIONS, ptr(self.state), ptr(self.ep_steps),
+                                 ptr(self.t_dev), ptr(self.stats), ptr(self.obs_ring), ptr(self.cur_slot),
+                                 ptr(self.eps), ptr(action_in), ptr(self.action), ptr(self.reward), ptr(self.done),
+                                 ptr(self.s0_h), ptr(self.s1_h), ptr(self.emit), ptr(self.row_s0), ptr(self.row_a),
+                                 ptr(self.row_s1), ptr(self.row_r), ptr(self.row_done), ptr(self.row_obs0),
+                                 ptr(self.row_obs1), ptr(self.q_out), self.seed, self.N, self.ring,
+                                 self.max_episode_steps)
+
+    @staticmethod
+    def columns(obs_dim=OBS_DIM):
+        return row_columns(obs_dim)

@@ -28,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import model
-from .mlp_actors import ENVS, NUM_ACTIONS, OBS_DIM, VecCartPoleActors, VecMlpActors
+from .mlp_actors import ENVS, VecMlpActors
 from .replay import HbmReplay
 from .schedule import Interval
 from .solver import Box, DQNSolver, Discrete
@@ -70,9 +70,6 @@ class MlpApexDQN:
         self.device = torch.device(device if device is not None else "cuda")
         _, obs_dim, num_actions, limit = ENVS[cfg.env]
         self.max_episode_steps = int(limit if cfg.max_episode_steps is None else cfg.max_episode_steps)
-        # CartPole keeps the actors it was brought up on (rth_mlp_actor_step); the other envs run
-        # the generic step (rth_env_actor_step)
-        self._cartpole = (obs_dim, num_actions) == (OBS_DIM, NUM_ACTIONS)
         torch.manual_seed(cfg.seed)
         self.solver = DQNSolver(Box(-1, 1, (obs_dim,)), Discrete(num_actions), gamma=cfg.gamma,
                                 clip_value=cfg.clip_value, double_q=cfg.double_q, dueling=True,
@@ -98,9 +95,6 @@ class MlpApexDQN:
         self._graph_keep = None
 
     def _make_actors(self, n, n_step, **kw):
-        if self._cartpole:
-            return VecCartPoleActors(n, n_step, self.cfg.gamma, max_episode_steps=self.max_episode_steps,
-                                     device=self.device, **kw)
         return VecMlpActors(self.cfg.env, n, n_step, self.cfg.gamma, max_episode_steps=self.max_episode_steps,
                             device=self.device, **kw)
 
@@ -193,7 +187,7 @@ class MlpApexDQN:
         more often than long ones.  One host read, at the end."""
         if metric not in ("length", "return"):
             raise ValueError('greedy_eval: metric is "length" or "return"')
-        if metric == "return" and self._cartpole:  # reward 1 a step: the return is the length
+        if metric == "return" and self.cfg.env.startswith("CartPole"):  # reward 1 a step: the return is the length
             metric = "length"
         ev = self._make_actors(n_envs, 1, eps=0.0, seed=seed)
         episodes, _, last = ev.episode_stats()

@@ -273,7 +273,7 @@ def test_struct_layout_matches_header():
 def test_modules_import_without_gpu():
     from reth_amd import mlp_actors, mlp_apex
 
-    assert issubclass(mlp_actors.VecMlpActors, mlp_actors.VecCartPoleActors) and mlp_apex.MlpApexDQN
+    assert issubclass(mlp_actors.VecCartPoleActors, mlp_actors.VecMlpActors) and mlp_apex.MlpApexDQN
     assert mlp_apex.MlpApexConfig().env == "CartPole-v0"
     assert {k: v[1:] for k, v in mlp_actors.ENVS.items()} == {
         "CartPole-v0": (4, 2, 200), "CartPole-v1": (4, 2, 500), "Acrobot-v1": (6, 3, 500),
