@@ -656,8 +656,10 @@ __global__ __launch_bounds__(256) void k_conv1_pack_bf16x3(const float *__restri
 // accumulator.  The nine bf16 MFMAs per fp32 product therefore sum exactly the same real
 // products as the fp32 MFMA's fmaf chain, accumulated in fp32 in a different order (9K terms
 // instead of K) -- the difference is summation order, as between any two fp32 GEMM tilings,
-// not precision.  (Bounded-exponent caveat: a term below 2^-126 would be a bf16 subnormal;
-// activations and weights of the DQN are many orders of magnitude away from that.)  Rate: 9
+// not precision.  (Exponent domain, measured -- tests/test_exact_split_gpu.py, DESIGN.md: exact
+// for values from 2^-110 up; below, the third term's last bits fall under the smallest bf16
+// subnormal, 2^-133 -- the MFMA honours bf16 subnormal operands -- and from (2 - 2^-8) 2^127 the
+// first term rounds to infinity.  The DQN's values are many orders of magnitude inside.)  Rate: 9
 // v_mfma_f32_16x16x32_bf16 (16 cycles each) do the work of 8 v_mfma_f32_16x16x4_f32 (32
 // cycles each): 144 vs 256 matrix-pipe cycles per 16 x 16 x 32 block, 1.78x.
 //

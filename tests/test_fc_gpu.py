@@ -3,7 +3,9 @@ Linear as one [512, 3136] weight) on the exact-split bf16 MFMA and on the fp32 M
 against a float64 CPU reference of relu(x w^T + b): within fp32 summation error (the products
 are exact; only the order of the fp32 sums differs from an fp32 GEMM), run-to-run
 bit-identical, every output written, the split-K and single-split paths, a strided x, no bias /
-no ReLU, and (rth_fc_f32) ragged row counts -- the actors' N + k live rows."""
+no ReLU, and (rth_fc_f32) ragged row counts -- the actors' N + k live rows.  That the products
+are exact is tested in test_exact_split_gpu.py, bit for bit, on inputs whose result no summation
+order changes; the bounds here see the summation error."""
 import numpy as np
 import pytest
 import torch
