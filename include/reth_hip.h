@@ -589,6 +589,24 @@ int rth_conv_dgrad_relu_supported(const rth_conv_shape *shape);
 int rth_conv_dgrad_relu_prepacked(const rth_conv_shape *shape, const float *gy_dev, int64_t n, const void *packed_dev,
                                   const float *y_dev, float *gx_dev, void *bias_ws_dev, int64_t *slabs_out,
                                   void *stream);
+/* rth_conv_dgrad_relu_prepacked reading FC1's data gradient where it lies (r15; conv3's geometry,
+ * rth_conv_dgrad_relu_nchw_supported): g_dev and y_dev are NCHW [n, 64, 7, 7], FC1's data
+ * gradient and conv3's own forward output.  The data-gradient launch does rth_relu_bias_grad_nchw's
+ * mask pass too: gy_dev [n, 7, 7, 64] NHWC = g where y > 0, else 0 (for the weight gradient),
+ * gx_dev = the data gradient of gy where y_below_dev (conv2's output, [n, 9, 9, 64] NHWC) > 0,
+ * else 0, and conv2's bias-gradient slabs in bias_ws_below_dev, finished by a rth_bias_deferred
+ * job whose `slabs` is *slabs_out -- all as rth_conv_dgrad_relu_prepacked writes them.  A second,
+ * small launch sums conv3's own bias-gradient slabs from gy_dev into bias_ws_dev in
+ * rth_relu_bias_grad_nchw's slab layout and order (finished by a job with `slabs` 0 and rows =
+ * n * 49).  Every output has the bits of rth_relu_bias_grad_nchw followed by
+ * rth_conv_dgrad_relu_prepacked.  Both workspaces are rth_relu_bias_grad workspaces of C = 64.
+ * Same preconditions as rth_conv_dgrad_relu_prepacked (16-byte alignment, n * 49 * 64 * 4 bytes
+ * < 2 GiB, at most 2048 slabs).  Reference: the backward of dqn_model.py:14-20 (Conv2d + ReLU,
+ * Flatten). */
+int rth_conv_dgrad_relu_nchw_supported(const rth_conv_shape *shape);
+int rth_conv_dgrad_relu_nchw_prepacked(const rth_conv_shape *shape, const float *g_dev, const float *y_dev, int64_t n,
+                                       const void *packed_dev, const float *y_below_dev, float *gy_dev, float *gx_dev,
+                                       void *bias_ws_dev, void *bias_ws_below_dev, int64_t *slabs_out, void *stream);
 /* FC1 of the dueling heads (the first Linear + ReLU of both branches, dqn_model.py:38-47, as
  * one [N, K] weight) on the exact-split bf16 MFMA: y [M, N] = act(x [M, K] w^T + b), x
  * row-major with row stride ldx, w row-major [N, K] (the Linear weight as stored), act = ReLU

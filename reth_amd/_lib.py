@@ -244,6 +244,9 @@ SIGNATURES = {
     "rth_conv_dgrad_relu_supported": (c_i32, [ctypes.POINTER(ConvShape)]),
     "rth_conv_dgrad_relu_prepacked": (c_i32, [ctypes.POINTER(ConvShape), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                               ctypes.POINTER(c_i64), c_vp]),
+    "rth_conv_dgrad_relu_nchw_supported": (c_i32, [ctypes.POINTER(ConvShape)]),
+    "rth_conv_dgrad_relu_nchw_prepacked": (c_i32, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                                   c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "rth_atari_create": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "rth_atari_destroy": (c_i32, [c_vp]),
     "rth_atari_step": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

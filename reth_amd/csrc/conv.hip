@@ -712,17 +712,30 @@ struct X9Geom {
 // channels 4q.. per quad q, each lane's float4s in order, then a fixed LDS tree over the lanes of
 // a quad -- k_relu_bias_grad's slab layout, finished by the same deferred bias job).  This
 // replaces rth_relu_bias_grad's launch between the two data gradients.
+// NCHW (r15, with MASK: conv3's data gradient straight from FC1's gradient): x is the gradient
+// of this layer's own ReLU output where FC1 left it, NCHW [n, CIN, HS, WS], and xmask that
+// output.  The staging applies the mask in registers -- threshold_backward(x, xmask, 0) --,
+// stores the masked gradient channels-last to xmasked (what the weight gradient reads; the
+// bits of rth_relu_bias_grad_nchw's) and splits the same registers into LDS.  A lane's four
+// channels are four dwords 4 HS WS bytes apart in each tensor; a wave instruction still covers 16
+// consecutive pixels of a channel (64 contiguous bytes).  This replaces rth_relu_bias_grad_nchw's
+// pass ahead of conv3's backward; this layer's bias-gradient slabs are summed from xmasked by
+// k_bias_slabs_nhwc in that pass's order (a slab's chain runs across samples, which no
+// per-workgroup sum can reproduce bit for bit).
 template <int KH, int KW, int S, int CIN, int HIN, int WIN, int NSAMP, int ROT, int KS, int PAD = 0, int COUT_ = 64,
-          int CLS = 0, int MASK = 0>
+          int CLS = 0, int MASK = 0, int NCHW = 0>
 __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float *__restrict__ x, int64_t n,
                                                                   const int64_t *__restrict__ n_dev, int nsamp,
                                                                   const u32x4 *__restrict__ wpk,
                                                                   const float *__restrict__ bias,
                                                                   float *__restrict__ y, int out_nchw,
                                                                   const float *__restrict__ ymask,
-                                                                  float *__restrict__ bpart) {
+                                                                  float *__restrict__ bpart,
+                                                                  const float *__restrict__ xmask,
+                                                                  float *__restrict__ xmasked) {
   static_assert(!MASK || (PAD > 0 && !CLS && (64 * (COUT_ / 16) * KS) % (COUT_ / 4) == 0),
                 "the masked epilogue is the NHWC data gradient's; every lane keeps one channel quad");
+  static_assert(!NCHW || MASK, "the NCHW staging is the masked data gradient's");
   using G = X9Geom<KH, KW, S, CIN, HIN, WIN, NSAMP, ROT, KS, COUT_>;
   if constexpr (CLS) wpk += (size_t)blockIdx.y * G::PACKED_U4;
   constexpr int HS = HIN - 2 * PAD, WS = WIN - 2 * PAD;  // the source image
@@ -777,7 +790,10 @@ __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float 
   const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(x), 0, (int)(n * (int64_t)(HS * WS * CIN) * 4), 0x00020000);
   const uint32_t xb0 = (uint32_t)(b0 * (int64_t)(HS * WS * CIN) * 4);
-  auto fetch = [&](int i, int r0, int rend) -> float4 {
+  // (NCHW: xmask through a resource of the same range; m = the slot's mask values)
+  const __amdgpu_buffer_rsrc_t m_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float *>(NCHW ? xmask : x), 0, (int)(n * (int64_t)(HS * WS * CIN) * 4), 0x00020000);
+  auto fetch = [&](int i, int r0, int rend, float4 &m) -> float4 {
     int rr, c4;
     slot_of(i, r0, rr, c4);
     bool ok = rr < rend && rr < rows;
@@ -786,14 +802,34 @@ __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float 
       const int s = rr / (HIN * WIN), rem = rr - s * (HIN * WIN), yy = rem / WIN - PAD, xx = rem % WIN - PAD;
       ok = ok && yy >= 0 && yy < HS && xx >= 0 && xx < WS;
       src = (s * HS + yy) * WS + xx;
+      if constexpr (NCHW) src = (s * CIN + 4 * c4) * (HS * WS) + yy * WS + xx;  // channel 4 c4's dword
+    }
+    if constexpr (NCHW) {  // four channels HS * WS floats apart (past the range they all read zero)
+      const uint32_t off = ok ? xb0 + (uint32_t)(src * 4) : 0x80000000u;
+      float4 v;
+      auto ld = [&](__amdgpu_buffer_rsrc_t r, int k) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off + k * (HS * WS * 4), 0, 0));
+      };
+      v.x = ld(x_rsrc, 0), v.y = ld(x_rsrc, 1), v.z = ld(x_rsrc, 2), v.w = ld(x_rsrc, 3);
+      m.x = ld(m_rsrc, 0), m.y = ld(m_rsrc, 1), m.z = ld(m_rsrc, 2), m.w = ld(m_rsrc, 3);
+      return v;
     }
     const uint32_t off = ok ? xb0 + (uint32_t)((src * (CIN / 4) + c4) * 16) : 0x80000000u;
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, off, 0, 0));
   };
-  auto commit = [&](float4 v, int i, int r0, int rend) {
+  auto commit = [&](float4 v, float4 m, int i, int r0, int rend) {
     int rr, c4;
     slot_of(i, r0, rr, c4);
     if (rr >= rend || rr >= rows) return;
+    if constexpr (NCHW) {
+      v.x = m.x > 0.0f ? v.x : 0.0f;  // threshold_backward(g, y, 0); a border slot stays zero
+      v.y = m.y > 0.0f ? v.y : 0.0f;
+      v.z = m.z > 0.0f ? v.z : 0.0f;
+      v.w = m.w > 0.0f ? v.w : 0.0f;
+      const int s = rr / (HIN * WIN), rem = rr - s * (HIN * WIN), yy = rem / WIN - PAD, xx = rem % WIN - PAD;
+      if (yy >= 0 && yy < HS && xx >= 0 && xx < WS)
+        *reinterpret_cast<float4 *>(xmasked + (((b0 + s) * HS + yy) * WS + xx) * (int64_t)CIN + 4 * c4) = v;
+    }
     uint2 tr[3];
     split3_x4(v, tr);
     uint2 *l2 = reinterpret_cast<uint2 *>(lds);
@@ -802,17 +838,18 @@ __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float 
     for (int t = 0; t < 3; ++t) l2[(t * NG * PLANE + unit) * 2 + (c4 & 1)] = tr[t];
   };
   {
-    float4 va[UA];
+    float4 va[UA], ma[NCHW ? UA : 1];
 #pragma unroll
-    for (int u = 0; u < UA; ++u) va[u] = fetch(tid + u * NT, 0, tid + u * NT < SA ? RA : 0);
+    for (int u = 0; u < UA; ++u) va[u] = fetch(tid + u * NT, 0, tid + u * NT < SA ? RA : 0, ma[NCHW ? u : 0]);
 #pragma unroll
     for (int u = 0; u < UA; ++u)
-      if (tid + u * NT < SA) commit(va[u], tid + u * NT, 0, RA);
+      if (tid + u * NT < SA) commit(va[u], ma[NCHW ? u : 0], tid + u * NT, 0, RA);
   }
-  float4 vb[UB];
+  float4 vb[UB], mb[NCHW ? UB : 1];
   if constexpr (SB > 0) {
 #pragma unroll
-    for (int u = 0; u < UB; ++u) vb[u] = fetch(tid + u * NT, RA, tid + u * NT < SB ? RA + RB_ : 0);
+    for (int u = 0; u < UB; ++u)
+      vb[u] = fetch(tid + u * NT, RA, tid + u * NT < SB ? RA + RB_ : 0, mb[NCHW ? u : 0]);
   }
   const float bl = bias ? bias[cb * 16 + (lane & 15)] : 0.0f;
   __syncthreads();
@@ -878,7 +915,7 @@ __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float 
     if constexpr (SB > 0) {
 #pragma unroll
       for (int u = 0; u < UB; ++u)
-        if (tid + u * NT < SB) commit(vb[u], tid + u * NT, RA, RA + RB_);
+        if (tid + u * NT < SB) commit(vb[u], mb[NCHW ? u : 0], tid + u * NT, RA, RA + RB_);
     }
     __syncthreads();
     load(QA);
@@ -990,6 +1027,45 @@ __global__ __launch_bounds__(64 * (COUT_ / 16) * KS) void k_conv_x9(const float 
     float4 *yo = reinterpret_cast<float4 *>(y + b0 * (int64_t)(COUT * PIX));
     const float4 *Fs = reinterpret_cast<const float4 *>(F);
     for (int i = tid; i < total4; i += NT) yo[i] = Fs[i];
+  }
+}
+
+// The bias-gradient slabs of rth_relu_bias_grad_nchw from the masked gradient it would have
+// written (gy, channels-last [n, P, C], C = 64, P = 49: k_conv_x9's NCHW staging stores it), bit
+// for bit: gridDim.x = bias_grad_slabs(n * P, C) slabs, slab s owns samples [s n / S, (s + 1) n / S),
+// lane t sums channel t / 4 over the positions of quarter t % 4 (13, 13, 13, 10) across the
+// slab's samples in (sample, position) order, then the four quarter sums in quarter order --
+// k_relu_bias_grad_nchw's chain, so a deferred job with slabs = 0 finishes the same db.  The loads
+// of up to UB samples (a slab has at most 3 unless the slab count is capped) are all in flight
+// before the first add: one memory round trip per slab, the adds in order behind it.
+__global__ __launch_bounds__(kBiasThreads) void k_bias_slabs_nhwc(const float *__restrict__ gy,
+                                                                   float *__restrict__ part, int64_t n) {
+  constexpr int C = 64, P = 49, Q = kBiasThreads / C, PQ = (P + Q - 1) / Q, UB = 3;
+  __shared__ float red[kBiasThreads];
+  const int tid = threadIdx.x, S = gridDim.x, c = tid / Q, qq = tid % Q;
+  const int64_t b0 = (int64_t)blockIdx.x * n / S, b1 = (int64_t)(blockIdx.x + 1) * n / S;
+  const int p0 = qq * PQ, np = (P - p0 < PQ ? P - p0 : PQ);
+  float acc = 0.0f;
+  for (int64_t b = b0; b < b1; b += UB) {
+    float v[UB][PQ];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      const float *src = gy + ((b + u < b1 ? b + u : b) * P + p0) * C + c;  // past the slab: a duplicate, unused
+#pragma unroll
+      for (int k = 0; k < PQ; ++k) v[u][k] = src[(k < np ? k : 0) * C];
+    }
+#pragma unroll
+    for (int u = 0; u < UB; ++u)
+#pragma unroll
+      for (int k = 0; k < PQ; ++k)
+        if (b + u < b1 && k < np) acc = radd(acc, v[u][k]);
+  }
+  red[tid] = acc;
+  __syncthreads();
+  if (tid < C) {
+    float sum = red[tid * Q];
+    for (int k = 1; k < Q; ++k) sum = radd(sum, red[tid * Q + k]);
+    part[(int64_t)blockIdx.x * C + tid] = sum;
   }
 }
 
@@ -1996,6 +2072,7 @@ static int64_t dgrad_x9_nsamp(int64_t n, int classes, const void *const *fn, int
   int64_t ns = 0;
   double best = 0.0;
   for (int64_t k = 1; k <= 3; ++k) {
+    if (!fn[k]) continue;  // not built
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn[k], threads, 0) != hipSuccess || per_cu < 1)
       per_cu = 1;
@@ -2009,42 +2086,42 @@ static int64_t dgrad_x9_nsamp(int64_t n, int classes, const void *const *fn, int
 
 static int launch_dgrad_x9(const void *fn, const float *gy, int64_t n, int64_t ns, int classes, int threads,
                            const u32x4 *wpk, float *gx, hipStream_t st, const float *ymask = nullptr,
-                           float *bpart = nullptr) {
+                           float *bpart = nullptr, const float *xmask = nullptr, float *xmasked = nullptr) {
   const int nsi = (int)ns;
   const int64_t grid = (n + ns - 1) / ns;
   const int64_t *n_dev = nullptr;
   const float *bias = nullptr;
   int out_nchw = 0;
-  void *args[] = {(void *)&gy,  (void *)&n,  (void *)&n_dev,    (void *)&nsi,   (void *)&wpk,
-                  (void *)&bias, (void *)&gx, (void *)&out_nchw, (void *)&ymask, (void *)&bpart};
+  void *args[] = {(void *)&gy,    (void *)&n,     (void *)&n_dev,   (void *)&nsi,    (void *)&wpk,
+                  (void *)&bias,  (void *)&gx,    (void *)&out_nchw, (void *)&ymask, (void *)&bpart,
+                  (void *)&xmask, (void *)&xmasked};
   RTH_HIP(hipLaunchKernel(fn, dim3((unsigned)grid, (unsigned)classes), dim3(threads), args, 0, st));
   return RTH_OK;
 }
 
-// w == NULL: user_ws already holds the packed kernel (rth_conv_pack_many's data-gradient job)
+// conv3's data gradient by mode -- kDgrad3Plain, kDgrad3Mask (+ the layer below's ReLU mask and
+// bias slabs), kDgrad3Nchw (+ its own mask, read in NCHW where FC1 left the gradient) -- and
+// samples per workgroup: each mode's cost model queries its own instantiations' occupancy
+// (kDgrad3Nchw at 3 samples is not built: its phase B holds 64 staging registers across phase
+// A's MFMA loop and spills)
+enum { kDgrad3Plain = 0, kDgrad3Mask = 1, kDgrad3Nchw = 2 };
+static const void *const *dgrad3_table(int mode) {
+#define RTH_D3(NS, ...) \
+  reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, NS, 3, X9_DGRAD3_KS, 2, ##__VA_ARGS__>)
+  static const void *const fn[3][4] = {{nullptr, RTH_D3(1), RTH_D3(2), RTH_D3(3)},
+                                       {nullptr, RTH_D3(1, 64, 0, 1), RTH_D3(2, 64, 0, 1), RTH_D3(3, 64, 0, 1)},
+                                       {nullptr, RTH_D3(1, 64, 0, 1, 1), RTH_D3(2, 64, 0, 1, 1), nullptr}};
+#undef RTH_D3
+  return fn[mode];
+}
 // the samples per workgroup of conv3's data gradient at n samples (= its grid's divisor)
-static int64_t dgrad3_nsamp(int64_t n, bool mask) {
-  const void *fn[4] = {nullptr, reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 1, 3, X9_DGRAD3_KS, 2>),
-                       reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 2, 3, X9_DGRAD3_KS, 2>),
-                       reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 3, 3, X9_DGRAD3_KS, 2>)};
-  const void *fm[4] = {
-      nullptr, reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 1, 3, X9_DGRAD3_KS, 2, 64, 0, 1>),
-      reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 2, 3, X9_DGRAD3_KS, 2, 64, 0, 1>),
-      reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 3, 3, X9_DGRAD3_KS, 2, 64, 0, 1>)};
-  return dgrad_x9_nsamp(n, 1, mask ? fm : fn, X9Dgrad3<1>::NT, (int)x9_wg_per_cu());
+static int64_t dgrad3_nsamp(int64_t n, int mode) {
+  return dgrad_x9_nsamp(n, 1, dgrad3_table(mode), X9Dgrad3<1>::NT, (int)x9_wg_per_cu());
 }
-static const void *dgrad3_fn(int64_t ns, bool mask) {
-  const void *fn[4] = {nullptr, reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 1, 3, X9_DGRAD3_KS, 2>),
-                       reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 2, 3, X9_DGRAD3_KS, 2>),
-                       reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 3, 3, X9_DGRAD3_KS, 2>)};
-  const void *fm[4] = {
-      nullptr, reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 1, 3, X9_DGRAD3_KS, 2, 64, 0, 1>),
-      reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 2, 3, X9_DGRAD3_KS, 2, 64, 0, 1>),
-      reinterpret_cast<const void *>(&k_conv_x9<3, 3, 1, 64, 11, 11, 3, 3, X9_DGRAD3_KS, 2, 64, 0, 1>)};
-  return mask ? fm[ns] : fn[ns];
-}
+// w == NULL: user_ws already holds the packed kernel (rth_conv_pack_many's data-gradient job)
 static int conv_dgrad_x9_conv3(const float *gy, int64_t n, const float *w, float *gx, void *user_ws, hipStream_t st,
-                               const float *ymask = nullptr, float *bpart = nullptr) {
+                               const float *ymask = nullptr, float *bpart = nullptr, const float *xmask = nullptr,
+                               float *xmasked = nullptr) {
   static u32x4 *ws[64] = {};
   constexpr int PK = X9Dgrad3<1>::PACKED_U4;
   u32x4 *wpk = static_cast<u32x4 *>(user_ws);
@@ -2056,9 +2133,10 @@ static int conv_dgrad_x9_conv3(const float *gy, int64_t n, const float *w, float
                        dim3(256), 0, st, w, wpk);
     RTH_LAUNCHED();
   }
-  const bool mask = ymask != nullptr;
-  const int64_t ns = dgrad3_nsamp(n, mask);
-  return launch_dgrad_x9(dgrad3_fn(ns, mask), gy, n, ns, 1, X9Dgrad3<1>::NT, wpk, gx, st, ymask, bpart);
+  const int mode = xmask ? kDgrad3Nchw : (ymask ? kDgrad3Mask : kDgrad3Plain);
+  const int64_t ns = dgrad3_nsamp(n, mode);
+  return launch_dgrad_x9(dgrad3_table(mode)[ns], gy, n, ns, 1, X9Dgrad3<1>::NT, wpk, gx, st, ymask, bpart, xmask,
+                         xmasked);
 }
 
 // conv2: gy [n, 9, 9, 64] -> gx [n, 20, 20, 32]; each class reads gy padded to 11 x 11 and
@@ -2349,7 +2427,7 @@ static int conv_bias_relu(const rth_conv_shape *shape, const void *x, const int6
     const float *no_mask = nullptr;
     float *no_part = nullptr;
     void *args[] = {(void *)&xf, (void *)&n, (void *)&n_dev, (void *)&ns, (void *)&w, (void *)&bias, (void *)&y,
-                    (void *)&out_nchw, (void *)&no_mask, (void *)&no_part};
+                    (void *)&out_nchw, (void *)&no_mask, (void *)&no_part, (void *)&no_mask, (void *)&no_part};
     RTH_HIP(hipLaunchKernel(l.x9fn[nsamp], dim3((unsigned)grid), dim3(l.waves * 64), args, 0, as_stream(stream)));
     return RTH_OK;
   }
@@ -2434,12 +2512,44 @@ int rth_conv_dgrad_relu_prepacked(const rth_conv_shape *shape, const float *gy, 
               "rth_conv_dgrad_relu_prepacked: misaligned buffer");
   *slabs_out = 0;
   if (n == 0) return RTH_OK;
-  const int64_t slabs = (n + dgrad3_nsamp(n, true) - 1) / dgrad3_nsamp(n, true);
+  const int64_t slabs = (n + dgrad3_nsamp(n, kDgrad3Mask) - 1) / dgrad3_nsamp(n, kDgrad3Mask);
   RTH_REQUIRE(slabs <= kBiasSlabs, "rth_conv_dgrad_relu_prepacked: %lld samples need %lld bias slabs (at most %d)",
               (long long)n, (long long)slabs, kBiasSlabs);
   *slabs_out = slabs;
   return conv_dgrad_x9_conv3(gy, n, nullptr, gx, const_cast<void *>(packed), as_stream(stream), y,
                              static_cast<float *>(bias_ws));
+}
+
+int rth_conv_dgrad_relu_nchw_supported(const rth_conv_shape *shape) { return shape && is_dgrad3_x9(shape) ? 1 : 0; }
+
+int rth_conv_dgrad_relu_nchw_prepacked(const rth_conv_shape *shape, const float *g, const float *y, int64_t n,
+                                       const void *packed, const float *y_below, float *gy, float *gx, void *bias_ws,
+                                       void *bias_ws_below, int64_t *slabs_out, void *stream) {
+  RTH_REQUIRE(shape && g && y && packed && y_below && gy && gx && bias_ws && bias_ws_below && slabs_out && n >= 0,
+              "rth_conv_dgrad_relu_nchw_prepacked: NULL argument");
+  RTH_REQUIRE(is_dgrad3_x9(shape),
+              "rth_conv_dgrad_relu_nchw_prepacked: only conv3's geometry (64x9x9, k3 s1) is built");
+  RTH_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(packed) |
+                reinterpret_cast<uintptr_t>(y_below) | reinterpret_cast<uintptr_t>(gy) |
+                reinterpret_cast<uintptr_t>(gx) | reinterpret_cast<uintptr_t>(bias_ws) |
+                reinterpret_cast<uintptr_t>(bias_ws_below)) &
+               15) == 0,
+              "rth_conv_dgrad_relu_nchw_prepacked: misaligned buffer");
+  *slabs_out = 0;
+  if (n == 0) return RTH_OK;
+  const int64_t ns = dgrad3_nsamp(n, kDgrad3Nchw), slabs = (n + ns - 1) / ns;
+  RTH_REQUIRE(slabs <= kBiasSlabs,
+              "rth_conv_dgrad_relu_nchw_prepacked: %lld samples need %lld bias slabs (at most %d)", (long long)n,
+              (long long)slabs, kBiasSlabs);
+  *slabs_out = slabs;
+  if (const int rc = conv_dgrad_x9_conv3(g, n, nullptr, gx, const_cast<void *>(packed), as_stream(stream), y_below,
+                                         static_cast<float *>(bias_ws_below), y, gy))
+    return rc;
+  // conv3's own slabs from gy in rth_relu_bias_grad_nchw's order (a deferred job with slabs = 0)
+  hipLaunchKernelGGL(k_bias_slabs_nhwc, dim3((unsigned)bias_grad_slabs(n * 49, 64)), dim3(kBiasThreads), 0,
+                     as_stream(stream), gy, static_cast<float *>(bias_ws), n);
+  RTH_LAUNCHED();
+  return RTH_OK;
 }
 
 int rth_conv_dgrad_ws(const rth_conv_shape *shape, const float *gy, int64_t n, const float *w, float *gx,

@@ -20,11 +20,14 @@
 // so a lane's loads are wide and the wave's 2 x NB accumulators (64 x GN outputs) take a pair
 // of pixels per 2 * NB MFMAs; PF pairs of loads are in flight ahead of their MFMAs, addressed by
 // an incremental cursor (adds and selects only).  The loads go through buffer resources over the
-// batch: a pixel past it reads zeros (contributes 0).  The waves' accumulators are added in LDS
-// in a fixed tree, one 32x32 block at a time, and wave 0 stores the workgroup's partial in the
-// accumulator order; the reduce (wgrad.hpp: k_conv_wgrad_f32_reduce here, or conv1's reduce
-// launch for a deferred job) adds the splits' partials in split order and scatters them to
-// OHWI.  Every sum has a fixed order: run to run bit-identical.
+// batch: a pixel past it reads zeros (contributes 0).  The waves' accumulators meet in LDS one
+// 32x32 block at a time: each wave stores its block, and behind one barrier all WAVES * 64
+// threads add the WAVES values of their elements in a fixed association and store the
+// workgroup's partial in the accumulator order, 8- or 16-byte runs per thread (r15; until then
+// a level-by-level tree with wave 0 alone doing the last adds and every store); the reduce
+// (wgrad.hpp: k_conv_wgrad_f32_reduce here, or conv1's reduce launch for a deferred job) adds
+// the splits' partials in split order and scatters them to OHWI.  Every sum has a fixed order:
+// run to run bit-identical.
 #include <type_traits>
 
 #include "common.hpp"
@@ -87,17 +90,21 @@ __device__ __forceinline__ void load_xvec(XVec<NB> &o, __amdgpu_buffer_rsrc_t r,
 }
 
 // WAVES waves per workgroup take consecutive quarters / eighths of the workgroup's pair range
-// and are summed in the fixed tree ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)), one 32x32
-// block at a time, each tree level in its own LDS slots (WAVES - 1 slots of 4 KB: one barrier
-// per level, and a block's slots are free again before the next block writes them)
+// and are summed in the fixed association ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)), one
+// 32x32 block at a time through WAVES LDS slots of 4 KB: every wave stores, every thread adds
+// and stores its share (r15; -DRTH_WGF_TREE builds r06's level-by-level tree, the same bits)
 template <int KH, int KW, int S, int CIN, int HIN, int WIN, int NB, int WAVES, int PF>
 __global__ __launch_bounds__(WAVES * 64) void k_conv_wgrad_f32(const float *__restrict__ x,
                                                               const float *__restrict__ gy, int n, int splits,
                                                               float *__restrict__ part) {
   using G = WgfGeom<KH, KW, S, CIN, HIN, WIN, NB>;
-  constexpr int PIX = G::PIX, WOUT = G::WOUT, HOUT_ = G::HOUT, LEVELS = WAVES == 8 ? 3 : WAVES == 4 ? 2 : 1;
+  constexpr int PIX = G::PIX, WOUT = G::WOUT, HOUT_ = G::HOUT;
   static_assert(WAVES == 2 || WAVES == 4 || WAVES == 8, "2, 4 or 8 waves");
+#ifndef RTH_WGF_TREE
+  __shared__ __attribute__((aligned(16))) float red[WAVES][1024];
+#else
   __shared__ float red[WAVES - 1][1024];
+#endif
   const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // workgroup -> (split, column group): the GROUPS workgroups of a split sit on one XCD
@@ -183,8 +190,36 @@ __global__ __launch_bounds__(WAVES * 64) void k_conv_wgrad_f32(const float *__re
   for (int d = 0; d < PF - 1; ++d)
     if (q + d < q1) mfmas(d);  // the last < PF pairs (wave-uniform)
 
-  // the waves' tree sum; wave 0 stores the partial [split][group][block][register][lane]
+  // the waves' sum, the partial stored as [split][group][block][register][lane]
   float *out = part + ((int64_t)split * G::GROUPS + grp) * G::TILE;
+#ifndef RTH_WGF_TREE
+  // one 32x32 block at a time: every wave stores its block to its own slot in the partial's
+  // order (register, lane); behind one barrier thread t adds elements [EPT t, EPT t + EPT) of
+  // the WAVES slots in the tree's association and stores them as one run (a wave: 64 EPT
+  // consecutive floats).  The second barrier frees the slots for the next block.
+  constexpr int EPT = 1024 / (WAVES * 64);
+  using fvec = __attribute__((ext_vector_type(EPT))) float;
+#pragma unroll
+  for (int blk = 0; blk < G::BLK; ++blk) {
+    const f32x16 &v = acc[blk / NB][blk % NB];
+    if (blk) __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][r * 64 + lane] = v[r];
+    __syncthreads();
+    const int e = EPT * (int)threadIdx.x;
+    fvec s[WAVES];
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) s[w] = *reinterpret_cast<const fvec *>(&red[w][e]);
+#pragma unroll
+    for (int span = 1; span < WAVES; span *= 2)  // ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7))
+#pragma unroll
+      for (int w = 0; w < WAVES; w += 2 * span)
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) s[w][k] = radd(s[w][k], s[w + span][k]);
+    *reinterpret_cast<fvec *>(out + blk * 1024 + e) = s[0];
+  }
+#else  // the r06 epilogue (A/B builds): an LDS tree, one barrier per level, wave 0 stores
+  constexpr int LEVELS = WAVES == 8 ? 3 : WAVES == 4 ? 2 : 1;
 #pragma unroll
   for (int blk = 0; blk < G::BLK; ++blk) {
     f32x16 &v = acc[blk / NB][blk % NB];
@@ -211,6 +246,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_conv_wgrad_f32(const float *__re
       base += WAVES >> (lv + 1);
     }
   }
+#endif
 }
 
 // gw = the sum of the splits' partials in split order (wgrad.hpp), scattered to OHWI
@@ -537,7 +573,8 @@ static int wgf_partials(const rth_conv_shape *shape, const float *x, int64_t n, 
                   n * ((shape->hin - shape->kh) / shape->stride + 1) * ((shape->win - shape->kw) / shape->stride + 1) *
                           shape->cout * 4 < ((int64_t)1 << 31),
               "rth_conv_wgrad_f32: batch too large");
-  RTH_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0,
+  RTH_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy) |
+                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
               "rth_conv_wgrad_f32: misaligned buffer");
   int ni = (int)n, splits = l.splits;
   float *part = static_cast<float *>(workspace);

@@ -24,6 +24,8 @@ path of solver.py (compute_grads with torch.autograd), without the autograd engi
 Only the first B rows of the 2B forward are differentiated: they are contiguous views
 (NHWC, batch-major), so the backward reads them in place.
 """
+import os
+
 import torch
 
 from . import _lib
@@ -34,7 +36,8 @@ from .replay import FrameStacks
 
 
 TD_HB_MAX = 16384  # rth_td_heads_backward keeps B * (A + 1) TD gradient rows in LDS
-# Module constants (tests patch them to run the alternative kernels; no environment switches):
+# Module constants (tests patch them to run the alternative kernels; no environment switches but
+# DGRAD_NCHW's, which an unmodified bench.py needs for its A/B):
 # HIP_DGRAD -- the layers whose data gradient runs on rth_conv_dgrad (the exact-split bf16 MFMA,
 # no zero fill) instead of MIOpen: conv2's (4 stride-parity classes in one launch) and conv3's
 # (0.570-0.574 vs 0.575-0.580 ms/step with MIOpen's, r04).
@@ -52,6 +55,16 @@ DGRAD_PREPACK = True
 # DGRAD_MASK -- conv3's data gradient applies conv2's ReLU mask and writes conv2's bias-gradient
 # slabs in its own epilogue (rth_conv_dgrad_relu_prepacked): one launch fewer per update
 DGRAD_MASK = True
+# DGRAD_NCHW -- with DGRAD_MASK on uint8 stacks: conv3's data gradient reads FC1's data gradient
+# and conv3's output in NCHW where they lie, applies conv3's own ReLU mask while it stages them
+# and writes the channels-last masked gradient for conv3's weight gradient
+# (rth_conv_dgrad_relu_nchw_prepacked, r15); a small launch behind it sums conv3's bias slabs from
+# that gradient in rth_relu_bias_grad_nchw's order.  The rth_relu_bias_grad_nchw pass over three
+# 6.4 MB tensors, alone on the critical path between FC1's and conv3's backward, is gone, and every
+# gradient keeps its bits (step 0.504 -> 0.495-0.498 ms together with r15's weight-gradient
+# epilogue; by itself inside the spread).  RTH_DGRAD_NCHW=0 in the environment, read once at
+# import, turns it off: the A/B arm of an unmodified bench.py (profiles/r15/conv_backward.txt)
+DGRAD_NCHW = os.environ.get("RTH_DGRAD_NCHW", "1") != "0"
 # NORM_IN_BACKWARD -- one rank, ClipAdam: clip_grad_norm_'s partials written by conv1's
 # weight-gradient reduce launch (extra workgroups over the gradients final before it, and the
 # squares of what it finishes itself), so the optimizer step is rth_adam_prenormed alone (r06)
@@ -254,7 +267,27 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                 break
             nb, c, hh, ww = y.shape
             defer = u8  # finished by conv1's rth_conv_relu_wgrad_ex
-            if fused_below is not None:  # masked and its bias slabs written by the data gradient above
+            xin = ys[li - 1][:B] if li > 0 else x[:B]
+            # the last conv's mask pass inside its masked data gradient (DGRAD_NCHW)
+            nchw_fused = li == len(convs) - 1 and li in dgp and li > 0 and defer and DGRAD_MASK and DGRAD_NCHW and \
+                li in HIP_DGRAD and fused_below is None and \
+                bool(_lib.lib().rth_conv_dgrad_relu_nchw_supported(ctypes.byref(shapes[li])))
+            gx = None
+            if nchw_fused:
+                gy = torch.empty((nb, c, hh, ww), dtype=torch.float32, device=x.device,
+                                 memory_format=torch.channels_last)
+                db = torch.empty(c, dtype=torch.float32, device=x.device)
+                gx = torch.empty(xin.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+                slabs = ctypes.c_int64(0)
+                call("rth_conv_dgrad_relu_nchw_prepacked", ctypes.byref(shapes[li]), ptr(g), ptr(y), B, ptr(dgp[li]),
+                     ptr(xin), ptr(gy), ptr(gx), ptr(rbws[li]), ptr(rbws[li - 1]), ctypes.byref(slabs), st)
+                deferred.append(_lib.BiasDeferred(rbws[li].data_ptr(), db.data_ptr(), nb * hh * ww, c, 0))
+                cb = convs[li - 1].out_channels
+                db_below = torch.empty(cb, dtype=torch.float32, device=x.device)
+                deferred.append(_lib.BiasDeferred(rbws[li - 1].data_ptr(), db_below.data_ptr(),
+                                                  xin.shape[0] * xin.shape[2] * xin.shape[3], cb, slabs.value))
+                fused_below = (gx, db_below)
+            elif fused_below is not None:  # masked and its bias slabs written by the data gradient above
                 gy, db = fused_below
                 fused_below = None
             else:
@@ -270,16 +303,16 @@ def dueling_grads(solver, s0, a, r, s1, done, isw, q1t=None, td_acc=None, mid=No
                          nb * hh * ww, c, st)
                 if defer:
                     deferred.append(_lib.BiasDeferred(rbws[li].data_ptr(), db.data_ptr(), nb * hh * ww, c, 0))
-            xin = ys[li - 1][:B] if li > 0 else x[:B]
             w = _nhwc(conv.weight.detach())
-            hip_dgrad = li in HIP_DGRAD and _lib.lib().rth_conv_dgrad_supported(ctypes.byref(shapes[li]))
+            hip_dgrad = not nchw_fused and li in HIP_DGRAD and _lib.lib().rth_conv_dgrad_supported(ctypes.byref(shapes[li]))
             hip_wgrad = bool(HIP_WGRAD) and getattr(_lib.lib(), f"rth_conv_wgrad_{HIP_WGRAD}_supported")(
                 ctypes.byref(shapes[li]))
-            need = [li > 0 and not hip_dgrad, not hip_wgrad, False]
-            gx = gw = None
+            need = [li > 0 and not hip_dgrad and not nchw_fused, not hip_wgrad, False]
+            gw = None
             if need[0] or need[1]:
-                gx, gw, _ = torch.ops.aten.convolution_backward(gy, xin, w, None, list(conv.stride), [0, 0], [1, 1],
+                gxm, gw, _ = torch.ops.aten.convolution_backward(gy, xin, w, None, list(conv.stride), [0, 0], [1, 1],
                                                                 False, [0, 0], 1, need)
+                gx = gxm if need[0] else gx
             if hip_wgrad:  # weight gradient in rth_conv_wgrad_{f32,x9} (deterministic, no zero fill)
                 gw = torch.empty(conv.weight.shape, dtype=torch.float32, device=x.device,
                                  memory_format=torch.channels_last)
