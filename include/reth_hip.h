@@ -989,6 +989,50 @@ int rth_soft_update(float *const *target, const float *const *source, const int6
                     double tau, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Device-resident continuous-control actors on DDPG's fused actor (csrc/ddpg_actor.hpp): one
+ * launch per env step of N envs, one kernel templated on the env:
+ *   RTH_DDPG_ENV_PENDULUM  Pendulum-v0  D = 3, Ad = 1, reward -cost, no terminal state
+ * Per env: the acting forward (rth_ddpg_act's action, bit for bit), Ornstein-Uhlenbeck noise on
+ * counter-based normal draws (utils/noise.py, utils/exploration.py:34-53; the draws' mapping is
+ * documented in csrc/ddpg_actor.hpp), action = (float) ((double) act_det + eps * x') without
+ * clipping, the dynamics of reth_amd/envs.py's host class in fp64 in its operation order, the
+ * time limit, the reset of a finished episode (env state from Philox(seed, env, t), noise back to
+ * mu) and the transition as a dense row.  eps = eps_start + (eps_end - eps_start) * k / eps_steps,
+ * k = min(t, eps_steps), t = t_dev[i] + 1 the env's own act count: the schedule advances once per
+ * launch.  No host synchronisation, no atomics; graph-capturable.
+ * ---------------------------------------------------------------------------------- */
+enum { RTH_DDPG_ENV_PENDULUM = 0 };
+typedef struct rth_ddpg_actor_args {
+  const float *const *actor;  /* the actor: HOST array of six device pointers (unused by the reset) */
+  int64_t env;                /* RTH_DDPG_ENV_* */
+  int64_t D, Ad, H1, H2;      /* D, Ad must be the env's; the shape one rth_ddpg_supported builds */
+  double *state;              /* [N, 4] fp64 env state; columns the env does not use stay 0 */
+  int32_t *ep_steps;          /* [N] steps of the running episode */
+  int64_t *t_dev;             /* [N] env steps taken (the Philox counter, the schedule's step) */
+  int64_t *stats;             /* [N, 3] finished episodes, sum of their lengths, last length */
+  double *ret_stats;          /* [N, 3] fp64: running return, sum of finished returns, last finished return */
+  double *noise;              /* [N, Ad] fp64 OU state */
+  float *cur_obs;             /* [N, LD] f32, LD = D rounded up to 4 (pad floats 0), 16-byte aligned: the
+                                 observation each env acts on next */
+  const float *action_in;     /* [N, Ad] nullable: overrides the noisy action (the noise still advances) */
+  float *act_det;             /* out [N, Ad] nullable: the noise-free action */
+  float *row_s0, *row_a, *row_r, *row_s1, *row_done; /* out, dense f32: [N, D], [N, Ad], [N], [N, D], [N] */
+  uint64_t seed;
+  int64_t N;
+  double mu, theta, sigma;    /* OUNoise */
+  double eps_start, eps_end;  /* the noise scale's linear schedule */
+  int64_t eps_steps;          /* >= 1 */
+  int32_t max_episode_steps;  /* TimeLimit: Pendulum-v0 200 */
+  int32_t reserved;
+} rth_ddpg_actor_args;
+/* env.reset() of every env: states from Philox(seed, env, t = 0), ep_steps / t_dev / stats /
+ * ret_stats = 0, noise = mu, the observation into cur_obs.  Arguments are checked before anything
+ * is launched (RTH_ERR_INVALID, rth_last_error). */
+int rth_ddpg_env_reset(const rth_ddpg_actor_args *args, void *stream);
+/* One env step of all N actors, one launch.  Arguments are checked before anything is launched. */
+int rth_ddpg_actor_step(const rth_ddpg_actor_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Learner -> actor weights: a device-resident latest-wins slot with a device version.
  * Replaces perwez's PUB/SUB CONFLATE weights channel (perwez/perwez/client/socket.py:19-122,
  * 302-328: SendSocket.send / RecvSocket.recv / RecvSocket.empty) as used by

@@ -113,6 +113,20 @@ class EnvActorArgs(ctypes.Structure):
                 ("max_episode_steps", c_i32)]
 
 
+DDPG_ENV_PENDULUM = 0  # RTH_DDPG_ENV_*
+
+
+class DdpgActorArgs(ctypes.Structure):
+    """rth_ddpg_actor_args"""
+    _fields_ = [("actor", ctypes.POINTER(c_vp)), ("env", c_i64), ("D", c_i64), ("Ad", c_i64), ("H1", c_i64),
+                ("H2", c_i64), ("state", c_vp), ("ep_steps", c_vp), ("t_dev", c_vp), ("stats", c_vp),
+                ("ret_stats", c_vp), ("noise", c_vp), ("cur_obs", c_vp), ("action_in", c_vp), ("act_det", c_vp),
+                ("row_s0", c_vp), ("row_a", c_vp), ("row_r", c_vp), ("row_s1", c_vp), ("row_done", c_vp),
+                ("seed", c_u64), ("N", c_i64), ("mu", c_f64), ("theta", c_f64), ("sigma", c_f64),
+                ("eps_start", c_f64), ("eps_end", c_f64), ("eps_steps", c_i64), ("max_episode_steps", c_i32),
+                ("reserved", c_i32)]
+
+
 # name -> (restype, argtypes); must match include/reth_hip.h exactly
 SIGNATURES = {
     "rth_last_error": (ctypes.c_char_p, []),
@@ -285,6 +299,9 @@ SIGNATURES = {
     # the classic-control family on the same step (env_actor.hpp)
     "rth_env_reset": (c_i32, [ctypes.POINTER(EnvActorArgs), c_vp]),
     "rth_env_actor_step": (c_i32, [c_vp, ctypes.POINTER(EnvActorArgs), c_vp]),
+    # the continuous-control actors on DDPG's actor (ddpg_actor.hpp)
+    "rth_ddpg_env_reset": (c_i32, [ctypes.POINTER(DdpgActorArgs), c_vp]),
+    "rth_ddpg_actor_step": (c_i32, [ctypes.POINTER(DdpgActorArgs), c_vp]),
     # learner -> actor weights slot (perwez PUB/SUB CONFLATE)
     "rth_weights_create": (c_i32, [c_i64, c_i32, ctypes.POINTER(c_vp)]),
     "rth_weights_destroy": (c_i32, [c_vp]),
