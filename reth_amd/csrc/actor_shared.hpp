@@ -1,6 +1,7 @@
 // Device functions of the actor side shared by actor.hip (the conv path's VecActors kernels) and
-// mlp_actor.hpp (the CartPole actors on the MLP kernels, compiled into qnet.hip): the ε-greedy
-// draws, the per-actor n-step adder and its handle.  One definition, two translation units.
+// the 1-D actor sets compiled into qnet.hip (env_actor.hpp, mlp_actor.hpp, ddpg_actor.hpp): the
+// per-env Philox block, the ε-greedy draws, the per-actor n-step adder and its handle.  One
+// definition, two translation units.
 //
 // Reference: reth/reth/utils/exploration.py:26-31 (RandomExploration.act),
 // reth/reth/utils/nstep_adder.py:5-28 (NStepAdder).
@@ -8,6 +9,14 @@
 #include "common.hpp"
 
 namespace rth {
+
+// ------------------------------------------------------------------ per-env draws
+// c = the Philox4x32-10 block of (seed, env i, step t, stream word w), a pure function of the four:
+// the reset draws and the OU normals of env_actor.hpp / ddpg_actor.hpp (their headers: the counter)
+__device__ __forceinline__ void env_philox_block(uint64_t seed, int64_t i, int64_t t, uint32_t w, uint32_t (&c)[4]) {
+  c[0] = (uint32_t)i, c[1] = (uint32_t)t, c[2] = (uint32_t)((uint64_t)t >> 32), c[3] = w;
+  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
 
 // ------------------------------------------------------------------ epsilon-greedy
 // the exploration draws of actor i at `counter`: the random action when u < eps_i, else -1 (act

@@ -96,8 +96,8 @@ struct DdpgActor {
 // ------------------------------------------------------------------ Pendulum
 __device__ inline void pendulum_reset_draw(uint64_t seed, int64_t i, int64_t t, double (&s)[4]) {
   const double pi = 3.141592653589793;
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_PENDULUM};
-  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  uint32_t c[4];
+  env_philox_block(seed, i, t, STREAM_PENDULUM, c);
   s[0] = radd(-pi, rmul(rmul(2.0, pi), (double)c[0]) / 4294967296.0);
   s[1] = radd(-1.0, rmul(2.0, (double)c[1]) / 4294967296.0);
   s[2] = 0.0, s[3] = 0.0;
@@ -156,8 +156,8 @@ __device__ inline void ou_normals(uint64_t seed, int64_t i, int64_t t, double (&
   const double two_pi = rmul(2.0, 3.141592653589793);
 #pragma unroll
   for (int b = 0; b < (Ad + 3) / 4; ++b) {
-    uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_OU | ((uint32_t)b << 16)};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    uint32_t c[4];
+    env_philox_block(seed, i, t, STREAM_OU | ((uint32_t)b << 16), c);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (4 * b + 2 * j >= Ad) break;
@@ -306,20 +306,13 @@ inline const char *ddpg_actor_check(const rth_ddpg_actor_args *x, bool step, Ddp
   return nullptr;
 }
 
-template <int ENV>
-inline void ddpg_actor_launch(bool step, const DdpgActor &a, hipStream_t st) {
-  if (step)
-    hipLaunchKernelGGL(k_ddpg_actor_step<ENV>, dim3(dense_grid(a.N)), dim3(kDdpgThreads), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_ddpg_env_reset<ENV>, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a);
-}
-
 // The body of both entry points: the checks, then the env's step or reset kernel.
 inline int ddpg_actor_run(const char *fn, const rth_ddpg_actor_args *x, bool step, void *stream) {
   DdpgActor a;
   const char *bad = ddpg_actor_check(x, step, &a);
   RTH_REQUIRE(!bad, "%s: %s", fn, bad);
-  ddpg_actor_launch<RTH_DDPG_ENV_PENDULUM>(step, a, as_stream(stream));  // the one env the check lets through
+  constexpr int ENV = RTH_DDPG_ENV_PENDULUM;  // the one env the check lets through
+  actor_launch<k_ddpg_actor_step<ENV>, k_ddpg_env_reset<ENV>, kDdpgThreads>(step, a, as_stream(stream));
   RTH_LAUNCHED();
   return RTH_OK;
 }

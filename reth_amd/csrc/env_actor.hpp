@@ -101,13 +101,6 @@ struct EnvActor {
 };
 
 // ------------------------------------------------------------------ CartPole
-__device__ inline void cartpole_reset_draw(uint64_t seed, int64_t i, int64_t t, double (&s)[4]) {
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_CARTPOLE};
-  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] = radd(-0.05, rmul(0.1, (double)c[k]) / 4294967296.0);
-}
-
 __device__ __forceinline__ float4 cartpole_obs(const double (&s)[4]) {
   return make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
 }
@@ -219,15 +212,15 @@ __device__ inline bool mountaincar_dynamics(double (&s)[4], int64_t action) {
 // ------------------------------------------------------------------ per-env pieces of the step
 __device__ inline void uniform_reset_draw(uint64_t seed, int64_t i, int64_t t, uint32_t stream, double lo,
                                           double width, int n, double (&s)[4]) {
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), stream};
-  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  uint32_t c[4];
+  env_philox_block(seed, i, t, stream, c);
 #pragma unroll
   for (int k = 0; k < 4; ++k) s[k] = k < n ? radd(lo, rmul(width, (double)c[k]) / 4294967296.0) : 0.0;
 }
 
 template <int ENV>
 __device__ __forceinline__ void env_reset_draw(uint64_t seed, int64_t i, int64_t t, double (&s)[4]) {
-  if constexpr (ENV == RTH_ENV_CARTPOLE) cartpole_reset_draw(seed, i, t, s);
+  if constexpr (ENV == RTH_ENV_CARTPOLE) uniform_reset_draw(seed, i, t, STREAM_CARTPOLE, -0.05, 0.1, 4, s);
   if constexpr (ENV == RTH_ENV_ACROBOT) uniform_reset_draw(seed, i, t, STREAM_ACROBOT, -0.1, 0.2, 4, s);
   if constexpr (ENV == RTH_ENV_MOUNTAINCAR) uniform_reset_draw(seed, i, t, STREAM_MOUNTAINCAR, -0.6, 0.2, 1, s);
 }
@@ -411,12 +404,19 @@ inline const char *env_actor_check(const rth_env_actor_args *x, const rth_nstep 
   return nullptr;
 }
 
+// the launch of an actor set's step kernel (workgroups of `Threads`, dense_grid over its N envs) or of
+// its reset kernel (one lane per env); ddpg_actor.hpp launches through it too
+template <auto Step, auto Reset, int Threads, class Actor>
+inline void actor_launch(bool step, const Actor &a, hipStream_t st) {
+  if (step)
+    hipLaunchKernelGGL(Step, dim3(dense_grid(a.N)), dim3(Threads), 0, st, a);
+  else
+    hipLaunchKernelGGL(Reset, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a);
+}
+
 template <int ENV>
 inline void env_launch(bool step, const EnvActor &a, hipStream_t st) {
-  if (step)
-    hipLaunchKernelGGL(k_env_actor_step<ENV>, dim3(dense_grid(a.N)), dim3(kMlpThreads), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_env_reset<ENV>, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a);
+  actor_launch<k_env_actor_step<ENV>, k_env_reset<ENV>, kMlpThreads>(step, a, st);
 }
 
 // The body of the four entry points: the checks, then the env's step (with the adder `h`) or reset

@@ -14,14 +14,15 @@ captured step replays.
 Every env is its own worker: its noise scale follows the schedule at the env's own act count, so
 the schedule advances once per step() -- not once per transition of the set.
 
-The counterpart of mlp_actors.VecMlpActors (discrete actions) for continuous ones.
+The counterpart of mlp_actors.VecMlpActors (discrete actions) for continuous ones; what the two
+share is device_loop.VecEnvActors.
 """
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .ddpg import H1, H2
+from .device_loop import VecEnvActors, as_tensor
 from .schedule import Schedule
 
 # env name -> (RTH_DDPG_ENV_* id, obs_dim, action_dim, TimeLimit) (csrc/ddpg_actor.hpp)
@@ -38,65 +39,42 @@ def _linear(epsilon):
     return float(s.start), float(s.end), int(s.max_steps)
 
 
-class VecDdpgActors:
+class VecDdpgActors(VecEnvActors):
     """N envs of `env` (a key of ENVS) stepped by one launch with the actor of a DDPGSolver (or a
     ddpg.Actor) at the env's (obs_dim, action_dim).  epsilon: the noise scale's schedule (a number
     or "start,end,steps"; 0 acts greedily); mu / theta / sigma: OUNoise's.  cur_obs rows are
     obs_dim rounded up to 4 floats (the pad stays 0); rows() are dense.  Episode statistics in
     int64 (episode_stats) and fp64 returns (return_stats).  max_episode_steps defaults to the
     env's TimeLimit."""
+    _envs = ENVS
 
     def __init__(self, env, n_actors, epsilon="1,0.01,30000", mu=0.0, theta=0.15, sigma=0.2, seed=0,
                  max_episode_steps=None, device=None):
-        if env not in ENVS:
-            raise ValueError(f"VecDdpgActors: unknown env {env!r} (device envs: {', '.join(ENVS)})")
-        self.env = self.name = env
-        self.env_id, self.obs_dim, self.action_dim, limit = ENVS[env]
-        self.ld = (self.obs_dim + 3) // 4 * 4  # cur_obs's row stride in floats
-        self.N = int(n_actors)
-        self.seed = int(seed)
-        self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
-        if self.N < 1 or self.max_episode_steps < 1:
-            raise ValueError("n_actors and max_episode_steps must be >= 1")
         self.mu, self.theta, self.sigma = float(mu), float(theta), float(sigma)
         self.eps_start, self.eps_end, self.eps_steps = _linear(epsilon)
-        self.device = torch.device(device if device is not None else "cuda")
-        N, D, Ad = self.N, self.obs_dim, self.action_dim
-        z = self._alloc
-        self.state = z((N, 4), torch.float64)
-        self.ep_steps = z((N,), torch.int32)
-        self.t_dev = z((N,), torch.int64)          # each env's act count (the Philox counter, the schedule's step)
-        self.stats = z((N, 3), torch.int64)        # finished episodes, sum of their lengths, last length
-        self.ret_stats = z((N, 3), torch.float64)  # running return, sum of finished returns, last finished return
+        super().__init__(env, n_actors, seed, max_episode_steps, device)  # (t_dev: also the schedule's step)
+        self.action_dim = ENVS[env][2]
+        N, D, Ad, z = self.N, self.obs_dim, self.action_dim, self._alloc
         self.noise = z((N, Ad), torch.float64)     # the OU state
         self.cur_obs = z((N, self.ld), torch.float32)
         self.act_det = z((N, Ad), torch.float32)   # the noise-free action of the last step
         self.row_s0, self.row_s1 = z((N, D), torch.float32), z((N, D), torch.float32)
         self.row_a = z((N, Ad), torch.float32)
         self.row_r, self.row_done = z((N,), torch.float32), z((N,), torch.float32)
-        self._params_key = self._params_arr = self._dims = None
-        self.pushes = 0    # env steps issued (host mirror of t_dev)
-        self.launches = 0  # actor-step calls: one launch each
+        self._dims = None  # the actor's (D, Ad, H1, H2), with the parameter cache
         self.reset()
-
-    def _alloc(self, shape, dtype):
-        """a zero-filled device buffer (tests override it to surround every buffer with guards)"""
-        return torch.zeros(shape, dtype=dtype, device=self.device)
 
     # ------------------------------------------------------------------ ABI arguments
     def _params(self, solver_or_actor):
-        actor = getattr(solver_or_actor, "actor", solver_or_actor)
-        ps = actor._params6()
-        key = tuple(p.data_ptr() for p in ps)
-        if key != self._params_key:
-            dims = tuple(int(v) for v in actor.dims())
-            ok = all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps)
-            if not ok or dims[:2] != (self.obs_dim, self.action_dim) or not _lib.lib().rth_ddpg_supported(*dims):
-                raise ValueError(f"the {self.name} actors run ddpg.Actor(({self.obs_dim},), ({self.action_dim},)) in "
-                                 f"contiguous float32 on the GPU, got dims (D, Ad, H1, H2) = {dims}")
-            self._params_arr = (_lib.c_vp * 6)(*key)
-            self._params_key, self._dims = key, dims
-        return self._params_arr
+        return super()._params(getattr(solver_or_actor, "actor", solver_or_actor))
+
+    def _check_net(self, actor, params):
+        dims = tuple(int(v) for v in actor.dims())
+        ok = all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params)
+        if not ok or dims[:2] != (self.obs_dim, self.action_dim) or not _lib.lib().rth_ddpg_supported(*dims):
+            raise ValueError(f"the {self.name} actors run ddpg.Actor(({self.obs_dim},), ({self.action_dim},)) in "
+                             f"contiguous float32 on the GPU, got dims (D, Ad, H1, H2) = {dims}")
+        self._dims = dims
 
     def _args(self, params=None, action_in=None, dims=None):
         # (the reset reads no network: it is given the reference's hidden widths to pass the shape check)
@@ -123,20 +101,15 @@ class VecDdpgActors:
         obs[:, 2] = state[:, 1].float()
         return obs
 
+    def _store_obs(self, obs):
+        self.cur_obs.copy_(obs)
+
     @torch.no_grad()
     def set_state(self, states, steps=None, noise=None):
-        """inject env states [N, 4] (float64; [N, k] fills the first k columns) and, optionally, the
-        running episodes' step counts [N] and the OU states [N, Ad]; the observations the envs act
-        on next become those of the states (tests)"""
-        as_t = lambda v: torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
-        st = as_t(states).to(self.device, torch.float64).reshape(self.N, -1)
-        self.state.zero_()
-        self.state[:, :st.shape[1]] = st
-        if steps is not None:
-            self.ep_steps.copy_(as_t(steps).to(self.device, torch.int32).reshape(self.N))
+        """VecEnvActors.set_state and, optionally, the OU states [N, Ad] (tests)"""
+        super().set_state(states, steps)
         if noise is not None:
-            self.noise.copy_(as_t(noise).to(self.device, torch.float64).reshape(self.N, self.action_dim))
-        self.cur_obs.copy_(self.observe(self.state))
+            self.noise.copy_(as_tensor(noise).to(self.device, torch.float64).reshape(self.N, self.action_dim))
 
     def current_obs(self):
         """the observations [N, obs_dim] the envs act on next (a dense copy)"""
@@ -147,9 +120,7 @@ class VecDdpgActors:
         """one env step for every actor, one launch, with the actor of a DDPGSolver (or a
         ddpg.Actor); action_in (float32 [N, Ad], device) overrides the noisy action"""
         if action_in is not None:
-            if not (torch.is_tensor(action_in) and action_in.is_cuda and action_in.dtype == torch.float32
-                    and action_in.numel() == self.N * self.action_dim and action_in.is_contiguous()):
-                raise ValueError("action_in: a contiguous float32 device tensor [N, Ad]")
+            self._check_action_in(action_in, torch.float32, self.N * self.action_dim, "float32 device tensor [N, Ad]")
         params = self._params(solver_or_actor)
         args = self._args(params, action_in, self._dims)
         call("rth_ddpg_actor_step", _lib.ctypes.byref(args), stream_ptr())
@@ -168,13 +139,3 @@ class VecDdpgActors:
 
         return [Column((self.obs_dim,), torch.float32), Column((self.action_dim,), torch.float32),
                 Column((), torch.float32), Column((self.obs_dim,), torch.float32), Column((), torch.float32)]
-
-    def episode_stats(self):
-        """per-env device statistics (int64 [N] each): finished episodes, the sum of their lengths,
-        the last finished length"""
-        return self.stats[:, 0], self.stats[:, 1], self.stats[:, 2]
-
-    def return_stats(self):
-        """per-env device statistics (float64 [N] each): the running episode's return, the sum of
-        the finished episodes' returns, the last finished return"""
-        return self.ret_stats[:, 0], self.ret_stats[:, 1], self.ret_stats[:, 2]

@@ -14,9 +14,10 @@ and without host synchronisation:
        update_priorities(idx, |td|)
 
 Which of the steps run is decided on the host from counts it already knows (every actor emits one
-row per step): nothing is read back.  capture() records the steady-state iteration as one HIP
-graph; every per-step scalar (env step counters, FIFO tail, Philox counters, the schedules, Adam's
-step counts) is device-resident, so the graph replays.
+row per step): nothing is read back.  capture() (device_loop.OneStreamLoop's, as iteration() and
+the counters are) records the steady-state iteration as one HIP graph; every per-step scalar (env
+step counters, FIFO tail, Philox counters, the schedules, Adam's step counts) is device-resident,
+so the graph replays.
 
 Every device env is its own worker, so the noise schedule advances once per iteration (per env
 step of each env), where the reference's single worker advances it once per transition.
@@ -31,7 +32,7 @@ import torch
 
 from .ddpg import DDPGSolver
 from .ddpg_actors import ENVS, VecDdpgActors
-from .replay import HbmReplay
+from .device_loop import OneStreamLoop
 from .solver import Box
 
 
@@ -57,18 +58,13 @@ class DdpgApexConfig:
     seed: int = 0
 
 
-class DdpgApex:
+class DdpgApex(OneStreamLoop):
+    _solver_counter, _solver_launches = "hip_launches", 3  # update_device's
+
     def __init__(self, cfg: DdpgApexConfig = None, device=None, impl=None):
         cfg = cfg if cfg is not None else DdpgApexConfig()
-        if cfg.sample_start < 1 or cfg.batch_size < 1:
-            raise ValueError("sample_start and batch_size must be >= 1")
-        if cfg.env not in ENVS:
-            raise ValueError(f"DdpgApexConfig.env {cfg.env!r}: the device envs are {', '.join(ENVS)}")
-        self.cfg = cfg
-        self.device = torch.device(device if device is not None else "cuda")
-        _, obs_dim, action_dim, limit = ENVS[cfg.env]
-        self.max_episode_steps = int(limit if cfg.max_episode_steps is None else cfg.max_episode_steps)
-        torch.manual_seed(cfg.seed)
+        super().__init__(cfg, device, ENVS)
+        _, obs_dim, action_dim, _ = ENVS[cfg.env]
         self.solver = DDPGSolver(Box(-1.0, 1.0, (obs_dim,)), Box(-2.0, 2.0, (action_dim,)), gamma=cfg.gamma,
                                  tau=cfg.tau, learning_rate_actor=cfg.learning_rate_actor,
                                  learning_rate_critic=cfg.learning_rate_critic, device=self.device,
@@ -77,19 +73,10 @@ class DdpgApex:
             raise RuntimeError("DdpgApex runs on DDPG's fused kernels: the solver's active path is "
                                f"{self.solver.impl_active!r} (impl={impl!r}); there is no torch fallback")
         self.actors = self._make_actors(cfg.n_actors, epsilon=cfg.epsilon, seed=cfg.seed)
-        self.replay = HbmReplay(cfg.capacity, self.actors.columns(), cfg.alpha, cfg.beta, self.device,
-                                seed=cfg.seed + 7919)
-        self.batch, self.idx, self.isw = self.replay.new_batch(cfg.batch_size)
+        self._make_replay()
         self._ones = torch.ones(cfg.n_actors, dtype=torch.float64, device=self.device)  # append_batch's priorities
         self._no_idx = torch.empty(0, dtype=torch.int64, device=self.device)
         self._no_w = torch.empty(0, dtype=torch.float32, device=self.device)
-        self.iterations = 0
-        self.env_steps = 0
-        self.rows_emitted = 0  # = rows appended: every step's N rows are stored
-        self.updates = 0
-        self.last_td = None  # the last update's |td| [B]: the solver's persistent buffer (a replay writes it too)
-        self._graph = None
-        self._graph_keep = None
 
     def _make_actors(self, n, **kw):
         c = self.cfg
@@ -97,10 +84,6 @@ class DdpgApex:
                              max_episode_steps=self.max_episode_steps, device=self.device, **kw)
 
     # ------------------------------------------------------------------ one iteration
-    def _learning(self):
-        """the update runs in this iteration: sample_start rows are stored (host counts only)"""
-        return min(self.rows_emitted, self.cfg.capacity) >= self.cfg.sample_start
-
     def _body(self, learn):
         """the device work of one iteration; returns the update's |td| or None"""
         act, rep = self.actors, self.replay
@@ -113,60 +96,6 @@ class DdpgApex:
         td = self.solver.update_device(self.batch, self.isw)
         rep.update_priorities(self.idx, td)
         return td
-
-    def iteration(self):
-        """one iteration on the current stream; never synchronises with the host"""
-        act, N = self.actors, self.actors.N
-        self.rows_emitted += N  # this step emits N rows
-        if self._graph is not None:
-            self._graph.replay()
-            # host mirrors of what the replayed launches advanced on the device
-            act.pushes += 1
-            act.launches += 1
-            self.solver.hip_launches += 3
-            self.replay.alpha.step()
-            self.replay.beta.step()
-            learned = True
-        else:
-            learned = self._learning()
-            self.last_td = self._body(learned)
-        self.iterations += 1
-        self.env_steps += N
-        if learned:
-            self.updates += 1
-
-    def run(self, iterations):
-        for _ in range(int(iterations)):
-            self.iteration()
-
-    # ------------------------------------------------------------------ graph
-    def graph_ready(self):
-        """the next iteration is the steady-state one: the update runs, and has run once (its
-        buffers exist)"""
-        return min(self.rows_emitted + self.actors.N, self.cfg.capacity) >= self.cfg.sample_start and self.updates >= 1
-
-    def capture(self):
-        """record the steady-state iteration (actor step, append, schedule step, sample, update,
-        priority update) as one HIP graph on a side stream; iteration() replays it from then on.
-        Capturing records and does not run the iteration.  After a capture the C library's host
-        mirrors of the replay counters (HbmReplay.info) no longer advance -- the device state
-        does; rows_emitted / updates here are the counts."""
-        if self._graph is not None:
-            return
-        if not self.graph_ready():
-            raise RuntimeError("capture() records the steady-state iteration: run iteration() until at least one "
-                               "update has run (graph_ready())")
-        act, solver, rep = self.actors, self.solver, self.replay
-        host = (act.pushes, act.launches, solver.hip_launches, rep.alpha.cur_step, rep.beta.cur_step)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-            keep = self._body(True)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        act.pushes, act.launches, solver.hip_launches, rep.alpha.cur_step, rep.beta.cur_step = host
-        self._graph, self._graph_keep = g, keep
-        self.last_td = keep
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()

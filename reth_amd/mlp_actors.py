@@ -11,7 +11,8 @@ out as ring handles and by value (row_obs0 / row_obs1 [N, obs_dim]), so
 DQNSolver.calc_loss_device and HbmReplay.append consume them as dense tensors.  No host
 synchronisation anywhere; every per-step scalar is device-resident, so a captured step replays.
 
-The counterpart of actors.VecActors (conv observations) for 1-D observations.
+The counterpart of actors.VecActors (conv observations) for 1-D observations; what it shares with
+ddpg_actors.VecDdpgActors is device_loop.VecEnvActors.
 
 VecMlpActors(env, n, ...) is the implementation, on rth_env_reset / rth_env_actor_step.
 VecCartPoleActors(n, ...) is the same set fixed to CartPole-v0 through the CartPole entry points
@@ -23,6 +24,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .actors import apex_epsilons
+from .device_loop import VecEnvActors
 
 OBS_DIM, NUM_ACTIONS = 4, 2  # CartPole's
 
@@ -40,42 +42,26 @@ def row_columns(obs_dim):
             Column((obs_dim,), torch.float32), Column((), torch.float32)]
 
 
-class VecMlpActors:
+class VecMlpActors(VecEnvActors):
     """N envs of `env` (a key of ENVS) stepped by one launch at the env's network shape
     (obs_dim, 128, num_actions), with the env's reward, terminal rule and observation map.  The
     ring's rows are obs_dim rounded up to 4 floats (the pad stays 0); rows() are dense
     [N, obs_dim].  Episode statistics in int64 (episode_stats) and fp64 returns (return_stats).
     max_episode_steps defaults to the env's TimeLimit."""
+    _envs = ENVS
     _reset_fn, _step_fn = "rth_env_reset", "rth_env_actor_step"
-    _keeps_returns = True
 
     def __init__(self, env, n_actors, n_step=1, gamma=0.99, eps=None, seed=0, max_episode_steps=None, nstep_mode=0,
                  device=None):
-        if env not in ENVS:
-            raise ValueError(f"VecMlpActors: unknown env {env!r} (device envs: {', '.join(ENVS)})")
-        self.env = self.name = env
-        self.env_id, self.obs_dim, self.num_actions, limit = ENVS[env]
-        self.ld = (self.obs_dim + 3) // 4 * 4  # the ring's row stride in floats
-        self.N = int(n_actors)
         self.n_step, self.gamma = int(n_step), float(gamma)
         self.gamma_n = float(np.float32(gamma ** n_step))
-        self.seed = int(seed)
-        self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
-        if self.N < 1 or self.n_step < 1 or self.max_episode_steps < 1:
-            raise ValueError("n_actors, n_step and max_episode_steps must be >= 1")
-        self.device = torch.device(device if device is not None else "cuda")
+        super().__init__(env, n_actors, seed, max_episode_steps, device, n_step=self.n_step)
+        self.num_actions = ENVS[env][2]
         ring = 4
         while ring < 2 * (self.n_step + 3):  # an emitted row's observations are at most n + 1 steps old, 2 slots a step
             ring *= 2
         self.ring = ring
-        N, D = self.N, self.obs_dim
-        z = self._alloc
-        self.state = z((N, 4), torch.float64)
-        self.ep_steps = z((N,), torch.int32)
-        self.t_dev = z((N,), torch.int64)          # env steps taken, one equal copy per env (the Philox counter)
-        self.stats = z((N, 3), torch.int64)        # finished episodes, sum of their lengths, last length
-        # running return, sum of the finished episodes' returns, last finished return
-        self.ret_stats = z((N, 3), torch.float64) if self._keeps_returns else None
+        N, D, z = self.N, self.obs_dim, self._alloc
         self.obs_ring = z((N * ring + 1, self.ld), torch.float32)  # zero-filled once; last row: the sink
         self.cur_slot = z((N,), torch.int64)
         e = apex_epsilons(N) if eps is None else np.array(np.broadcast_to(np.asarray(eps, np.float64), (N,)))
@@ -95,14 +81,7 @@ class VecMlpActors:
             call("rth_nstep_create", N, self.n_step, self.gamma, int(nstep_mode), torch.cuda.current_device(),
                  _lib.ctypes.byref(h))
         self._nstep = h.value
-        self._params_key = self._params_arr = None
-        self.pushes = 0    # env steps issued (host mirror of t_dev)
-        self.launches = 0  # actor-step calls: one launch each
         self.reset()
-
-    def _alloc(self, shape, dtype):
-        """a zero-filled device buffer (tests override it to surround every buffer with guards)"""
-        return torch.zeros(shape, dtype=dtype, device=self.device)
 
     def __del__(self):
         if getattr(self, "_nstep", None):
@@ -113,17 +92,11 @@ class VecMlpActors:
             self._nstep = None
 
     # ------------------------------------------------------------------ ABI arguments
-    def _params(self, q_network):
-        ps = q_network._params6()
-        key = tuple(p.data_ptr() for p in ps)
-        if key != self._params_key:
-            want = (self.obs_dim, 128, self.num_actions)
-            if not q_network.hip_supported() or q_network.dims() != want:
-                raise ValueError(f"the {self.name} actors run MLP_DQNNetwork(({want[0]},), {want[2]}) on the GPU, got "
-                                 f"dims {q_network.dims()}")
-            self._params_arr = (_lib.c_vp * 6)(*key)
-            self._params_key = key
-        return self._params_arr
+    def _check_net(self, q_network, params):
+        want = (self.obs_dim, 128, self.num_actions)
+        if not q_network.hip_supported() or q_network.dims() != want:
+            raise ValueError(f"the {self.name} actors run MLP_DQNNetwork(({want[0]},), {want[2]}) on the GPU, got "
+                             f"dims {q_network.dims()}")
 
     def _args(self, params=None, action_in=None):
         return _lib.EnvActorArgs(params, self.env_id, self.obs_dim, 128, self.num_actions, ptr(self.state),
@@ -160,19 +133,8 @@ class VecMlpActors:
             obs[:, :self.obs_dim] = state[:, :self.obs_dim].float()
         return obs
 
-    @torch.no_grad()
-    def set_state(self, states, steps=None):
-        """inject env states [N, 4] (float64; [N, k] fills the first k columns) and, optionally, the
-        running episodes' step counts [N]; the observations the envs act on next become those of
-        the states (tests)"""
-        st = torch.as_tensor(np.asarray(states, np.float64) if not torch.is_tensor(states) else states)
-        st = st.to(self.device, torch.float64).reshape(self.N, -1)
-        self.state.zero_()
-        self.state[:, :st.shape[1]] = st
-        if steps is not None:
-            sp = torch.as_tensor(np.asarray(steps) if not torch.is_tensor(steps) else steps)
-            self.ep_steps.copy_(sp.to(self.device, torch.int32).reshape(self.N))
-        self.obs_ring[self._base + self.cur_slot] = self.observe(self.state)
+    def _store_obs(self, obs):
+        self.obs_ring[self._base + self.cur_slot] = obs
 
     def current_obs(self):
         """the observations [N, obs_dim] the envs act on next (a dense copy)"""
@@ -188,9 +150,7 @@ class VecMlpActors:
         """one env step for every actor, one launch; action_in (int64 [N], device) overrides the
         ε-greedy choice.  Returns True when rows were emitted (warm)."""
         if action_in is not None:
-            if not (torch.is_tensor(action_in) and action_in.is_cuda and action_in.dtype == torch.int64
-                    and action_in.numel() == self.N and action_in.is_contiguous()):
-                raise ValueError("action_in: a contiguous int64 device tensor [N]")
+            self._check_action_in(action_in, torch.int64, self.N, "int64 device tensor [N]")
         args = self._args(self._params(q_network), action_in)
         call(self._step_fn, self._nstep, _lib.ctypes.byref(args), stream_ptr())
         self.launches += 1
@@ -208,16 +168,6 @@ class VecMlpActors:
         if not self.warm:
             raise RuntimeError("no rows yet: the adders fill during the first n_step steps")
         return replay.append(self.rows(), td_abs)
-
-    def episode_stats(self):
-        """per-env device statistics (int64 [N] each): finished episodes, the sum of their lengths,
-        the last finished length"""
-        return self.stats[:, 0], self.stats[:, 1], self.stats[:, 2]
-
-    def return_stats(self):
-        """per-env device statistics (float64 [N] each): the running episode's return, the sum of
-        the finished episodes' returns, the last finished return"""
-        return self.ret_stats[:, 0], self.ret_stats[:, 1], self.ret_stats[:, 2]
 
     def columns(self):
         """replay columns of the rows [s0, a, r, s1, done] at this env's obs_dim"""

@@ -15,9 +15,10 @@ presets/worker.py:128-155.  One iteration, entirely in HBM and without host sync
 
 Which of the steps run is decided on the host from counts it already knows (every actor emits
 one row per step once warm): nothing is read back.  The target sync runs on the host Interval
-outside the iteration, as ApexDQN does it.  capture() records the steady-state iteration as one
-HIP graph; every per-step scalar (env step counters, FIFO tail, Philox counters, the schedules,
-Adam's step count) is device-resident, so the graph replays.
+outside the iteration, as ApexDQN does it.  capture() (device_loop.OneStreamLoop's, as iteration()
+and the counters are) records the steady-state iteration as one HIP graph; every per-step scalar
+(env step counters, FIFO tail, Philox counters, the schedules, Adam's step count) is
+device-resident, so the graph replays.
 
 The loop needs the MLP's fused kernels (model.MLP_IMPL = "hip"): without them it refuses to
 construct -- there is no torch fallback here.
@@ -28,8 +29,8 @@ from typing import Optional
 import torch
 
 from . import model
+from .device_loop import OneStreamLoop
 from .mlp_actors import ENVS, VecMlpActors
-from .replay import HbmReplay
 from .schedule import Interval
 from .solver import Box, DQNSolver, Discrete
 
@@ -56,21 +57,16 @@ class MlpApexConfig:
     env: str = "CartPole-v0"           # a key of mlp_actors.ENVS: the reference's env.name (examples/dqn/config.yaml)
 
 
-class MlpApexDQN:
+class MlpApexDQN(OneStreamLoop):
+    _solver_counter, _solver_launches = "mlp_hip_launches", 2  # calc_loss_device + update_device
+
     def __init__(self, cfg: MlpApexConfig = None, device=None):
         cfg = cfg if cfg is not None else MlpApexConfig()
         if model.MLP_IMPL != "hip":
             raise RuntimeError('MlpApexDQN runs on the fused MLP kernels: set reth_amd.model.MLP_IMPL = "hip" before '
                                f"constructing it (MLP_IMPL is {model.MLP_IMPL!r}); there is no torch fallback")
-        if cfg.sample_start < 1 or cfg.batch_size < 1:
-            raise ValueError("sample_start and batch_size must be >= 1")
-        if cfg.env not in ENVS:
-            raise ValueError(f"MlpApexConfig.env {cfg.env!r}: the device envs are {', '.join(ENVS)}")
-        self.cfg = cfg
-        self.device = torch.device(device if device is not None else "cuda")
-        _, obs_dim, num_actions, limit = ENVS[cfg.env]
-        self.max_episode_steps = int(limit if cfg.max_episode_steps is None else cfg.max_episode_steps)
-        torch.manual_seed(cfg.seed)
+        super().__init__(cfg, device, ENVS)
+        _, obs_dim, num_actions, _ = ENVS[cfg.env]
         self.solver = DQNSolver(Box(-1, 1, (obs_dim,)), Discrete(num_actions), gamma=cfg.gamma,
                                 clip_value=cfg.clip_value, double_q=cfg.double_q, dueling=True,
                                 learning_rate=cfg.learning_rate, adam_epsilon=cfg.adam_epsilon,
@@ -78,31 +74,18 @@ class MlpApexDQN:
                                 n_step=cfg.n_step)
         if self.solver.mlp_impl_active != "hip":
             raise RuntimeError("the MLP's HIP kernels are not active for this solver (rth_mlp_supported)")
-        # the target sync: host Interval outside the (possibly captured) iteration
+        # the target sync: host Interval outside the (possibly captured) iteration, after every update
         self.solver.auto_target_update = False
-        self._target_interval = Interval(self.solver.update_target, cfg.update_target_interval)
+        self._updated = Interval(self.solver.update_target, cfg.update_target_interval)
         self.actors = self._make_actors(cfg.n_actors, cfg.n_step, eps=cfg.eps, seed=cfg.seed,
                                         nstep_mode=cfg.nstep_mode)
-        self.replay = HbmReplay(cfg.capacity, self.actors.columns(), cfg.alpha, cfg.beta, self.device,
-                                seed=cfg.seed + 7919)
-        self.batch, self.idx, self.isw = self.replay.new_batch(cfg.batch_size)
-        self.iterations = 0
-        self.env_steps = 0
-        self.rows_emitted = 0  # = rows appended: every emitted row is stored
-        self.updates = 0
-        self.solver_calls = 0  # calc_loss_device + update_device calls issued (solver.mlp_hip_launches)
-        self._graph = None
-        self._graph_keep = None
+        self._make_replay()
 
     def _make_actors(self, n, n_step, **kw):
         return VecMlpActors(self.cfg.env, n, n_step, self.cfg.gamma, max_episode_steps=self.max_episode_steps,
                             device=self.device, **kw)
 
     # ------------------------------------------------------------------ one iteration
-    def _learning(self):
-        """the update runs in this iteration: sample_start rows are stored (host counts only)"""
-        return min(self.rows_emitted, self.cfg.capacity) >= self.cfg.sample_start
-
     def _body(self, learn):
         """the device work of one iteration with warm actors; returns the update's |td| or None"""
         act = self.actors
@@ -116,66 +99,18 @@ class MlpApexDQN:
         self.replay.update_priorities(self.idx, td_b, step=True)
         return td_b
 
-    def iteration(self):
-        """one iteration on the current stream; never synchronises with the host"""
-        act, N = self.actors, self.actors.N
-        if self._graph is not None:
-            self._graph.replay()
-            act.pushes += 1
-            act.launches += 1
-            self.rows_emitted += N
-            # host mirrors of what the replayed launches advanced on the device
-            self.solver.mlp_hip_launches += 2
-            self.solver_calls += 2
-            self.replay.alpha.step()
-            self.replay.beta.step()
-            learned = True
-        elif act.pushes < act.n_step:  # the adders fill: this step emits no rows yet
-            act.step(self.solver.q_network)
-            learned = False
-        else:
-            self.rows_emitted += N  # this step emits N rows
-            learned = self._learning()
-            self._body(learned)
-            self.solver_calls += 2 if learned else 1
-        self.iterations += 1
-        self.env_steps += N
-        if learned:
-            self.updates += 1
-            self._target_interval()
+    def _filling(self):
+        """the adders fill: the next step emits no rows yet"""
+        return self.actors.pushes < self.actors.n_step
 
-    def run(self, iterations):
-        for _ in range(int(iterations)):
-            self.iteration()
+    def _fill(self):
+        self.actors.step(self.solver.q_network)
 
-    # ------------------------------------------------------------------ graph
-    def graph_ready(self):
-        """the next iteration is the steady-state one: rows flow and the update runs"""
-        return self.actors.pushes >= self.actors.n_step and \
-            min(self.rows_emitted + self.actors.N, self.cfg.capacity) >= self.cfg.sample_start and self.updates >= 1
-
-    def capture(self):
-        """record the steady-state iteration (actor step, priorities, append, sample, update,
-        priority update) as one HIP graph on a side stream; iteration() replays it from then
-        on.  Capturing records and does not run the iteration.  After a capture the C library's
-        host mirrors of the replay counters (HbmReplay.info) no longer advance -- the device
-        state does; rows_emitted / updates here are the counts."""
-        if self._graph is not None:
-            return
-        if not self.graph_ready():
-            raise RuntimeError("capture() records the steady-state iteration: run iteration() until at least one "
-                               "update has run (graph_ready())")
-        act, solver, rep = self.actors, self.solver, self.replay
-        host = (act.pushes, act.launches, solver.mlp_hip_launches, rep.alpha.cur_step, rep.beta.cur_step)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-            keep = self._body(True)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        act.pushes, act.launches, solver.mlp_hip_launches, rep.alpha.cur_step, rep.beta.cur_step = host
-        self._graph, self._graph_keep = g, keep
-
+    @property
+    def solver_calls(self):
+        """calc_loss_device (one per iteration that emits rows) + update_device calls issued: what
+        solver.mlp_hip_launches counts"""
+        return self.rows_emitted // self.actors.N + self.updates
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()
     def greedy_eval(self, n_envs=256, seed=12345, max_steps=None, metric="length"):
