@@ -51,11 +51,6 @@ const char *rth_last_error(void);
  * levels above the subtree roots unwritten rather than maintaining them from stale sums).
  * Expected 0; the tests assert it. */
 int rth_tree_update_timeouts(int64_t *out);
-/* development aid (a library built with -DRTH_CLOCK_STAMPS only; the product build returns an
- * error): per workgroup of the last fp32-MFMA conv launch (k_conv_bias_relu), the shader-clock
- * and 100 MHz wall-clock ticks around wave 0's work -- out[2 i], out[2 i + 1] for workgroups
- * i < slots <= 1024 -- whose ratio is the in-kernel clock */
-int rth_debug_conv_clock(unsigned long long *out, int32_t slots);
 /* library build/ABI version (major*10000 + minor*100 + patch) */
 int rth_version(void);
 /* the source tree the library was compiled from: 40 hex digits, the SHA-1 over the lines
@@ -532,9 +527,9 @@ typedef struct rth_conv_shape {
   int32_t cin, hin, win, cout, kh, kw, stride;
 } rth_conv_shape;
 int rth_conv_supported(const rth_conv_shape *shape);
-/* which kernel rth_conv_bias_relu runs for a shape and n samples (hybrid geometries switch by
- * batch size): RTH_CONV_IMPL_F32 (k_conv_bias_relu, fp32 MFMA), RTH_CONV_IMPL_BF16X3
- * (k_conv1_u8_bf16x3), RTH_CONV_IMPL_X9 (k_conv_x9: both operands split into three exact bf16
+/* which kernel rth_conv_bias_relu runs for a shape and n samples: RTH_CONV_IMPL_F32
+ * (k_conv_bias_relu, fp32 MFMA), RTH_CONV_IMPL_BF16X3 (k_conv1_u8_share: conv1 on uint8 stacks,
+ * the weights split into three exact bf16 terms), RTH_CONV_IMPL_X9 (k_conv_x9: both operands split into three exact bf16
  * terms, nine bf16 MFMAs per fp32 product; *nsamp_out = samples per workgroup); 0 = not built.
  * Diagnostics (bench.py's roofline labels), no launch. */
 #define RTH_CONV_IMPL_F32 1

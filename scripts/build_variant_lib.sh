@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B variant of the library: the product sources with extra -D flags, into
 # reth_amd/libreth_hip_<name>.so (git-ignored; loaded through RTH_LIB_PATH, never by default)
-#   scripts/build_variant_lib.sh wg128 -DCONV_WG_BLOCKS=128
+#   scripts/build_variant_lib.sh wgftree -DRTH_WGF_TREE
 set -eu
 cd "$(dirname "$0")/.."
 name=$1; shift

@@ -47,11 +47,8 @@ for step in "$@"; do
              if [ $v = hip ]; then export RTH_HIP_DGRAD=1; else unset RTH_HIP_DGRAD; fi
              RTH_BENCH_SPAN=1 run bench_span_$v 600 python bench.py --steps 400 --warmup 20 --no-cpu-baseline; done
           unset RTH_HIP_DGRAD ;;
-    knobs) for w in 1 3 2; do RTH_CONV_WG_PER_CU=$w run bench_wpc$w 600 python bench.py --steps 400 --warmup 20 --no-cpu-baseline; done
-           for pr in 0 -1; do RTH_LEARNER_PRIORITY=$pr run bench_prio$pr 600 python bench.py --steps 400 --warmup 20 --no-cpu-baseline; done ;;
     convb) run bench_conv 300 python scripts/bench_conv.py ;;
     wgv) for v in build/variants/*.so; do b=$(basename $v .so); RTH_LIB_PATH=$PWD/$v run bench_wgrad_$b 300 python scripts/bench_wgrad.py; done ;;
-    convwpc) for w in 1 2 3 4; do RTH_CONV_WG_PER_CU=$w run bench_conv_wpc$w 300 python scripts/bench_conv.py; done ;;
     convv) for v in build/variants/*.so; do b=$(basename $v .so); RTH_LIB_PATH=$PWD/$v run bench_conv_$b 300 python scripts/bench_conv.py; done ;;
     convprof) export TMPDIR=/tmp; run prof_conv 300 rocprofv3 --kernel-trace --output-format csv \
             -d "$PWD/gpurun_out/prof_conv" -o run -- python scripts/bench_conv.py ;;

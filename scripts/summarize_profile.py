@@ -62,7 +62,7 @@ def is_conv(pats, name):
 
 def tree_pmc(dirs):
     """--tree-pmc DIR...: k_tree_sample's FETCH_SIZE per dispatch (x2, gfx950) by grid, one line
-    per variant directory (scripts/r04.sh treepmc)"""
+    per variant directory (the r04 treepmc passes)"""
     for d in dirs:
         p = os.path.join(d, "run_counter_collection.csv")
         if not os.path.exists(p):
