@@ -984,6 +984,56 @@ int rth_soft_update(float *const *target, const float *const *source, const int6
                     double tau, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * PPO's actor and value network (ppo_model.py:6-40) as fused fp32 kernels (ppo.hpp):
+ *   actor  Linear (D -> H), tanh, Linear (H -> H), tanh, Linear (H -> A), softmax
+ *   value  Linear (D -> H), tanh, Linear (H -> H), tanh, Linear (H -> 1)
+ * A network is a HOST array of six device pointers in torch layout, read in place (rth_mlp_q's
+ * `params`: {0.weight, 0.bias, 2.weight, 2.bias, 4.weight, 4.bias} of the Sequential); gradients
+ * have the same order and shapes (every element written, nothing accumulated).  Built for H = 64,
+ * D in 1..64, A in 2..18, any n (rth_ppo_act: up to 2^32), B >= 1; every entry point returns
+ * RTH_ERR_INVALID for another shape or a row stride below D and launches nothing.
+ * Every product is one fp32 fmaf and a dot product has one fixed summation order; tanh, exp and
+ * log are evaluated in fp64 and rounded once.  The policy is the log-softmax of the logits z: with
+ * m = max_j z_j and s = sum_j exp(z_j - m) (fp64, increasing j), logp_j = fl32((z_j - m) - log s)
+ * and p_j = fl32(exp(logp_j)).  The reference builds Categorical(probs = softmax(z)), which clamps
+ * the probabilities to [1.19e-7, 1 - 1.19e-7] before taking their logarithm; this form has no
+ * such clamp, so the two differ where a probability leaves that range (and nowhere else beyond
+ * rounding).  One forward and one log-softmax serve both entry points: a row's log-probability
+ * does not depend on n, on the row's position, on the row stride or on the entry point.
+ * Inputs are fp32 matrices with unit column stride and the given row stride (in floats).  All
+ * launches go to `stream`, without host synchronisation or allocation.
+ * ---------------------------------------------------------------------------------- */
+int rth_ppo_supported(int64_t D, int64_t H, int64_t A); /* 1 where built, else 0 */
+int64_t rth_ppo_workspace(int64_t B, int64_t D, int64_t H, int64_t A); /* bytes for rth_ppo_grads; < 0: error */
+/* ppo_solver.py:102-109 for n states, one launch: probs = actor(x) (probs_dev [n, A] dense,
+ * nullable), one Categorical draw per row by inverse CDF -- c_j = fl32(c_{j-1} + p_j) in increasing
+ * j, action = the first j with (double) c_j > u, or A - 1 if there is none -- and logprob =
+ * logp_action.  u = uniforms_dev[row] (double in [0, 1)) where given, else the Philox4x32-10
+ * uniform (53 bits, csrc/common.hpp philox_uniform) of (seed, counter, lane = row, stream word 13). */
+int rth_ppo_act(const float *const *actor, const float *x_dev, int64_t ldx, int64_t n, int64_t D, int64_t H, int64_t A,
+                const double *uniforms_dev, uint64_t seed, uint64_t counter, int64_t *action_dev, float *logprob_dev,
+                float *probs_dev, void *stream);
+/* One epoch of ppo_solver.py:72-96 for both networks.  With v_b = value(s_b), adv_b = ret_b - v_b,
+ * rho_b = exp(logp_b[a_b] - old_logprob_b), H_b = -sum_j p_bj logp_bj and mse = (1/B) sum_b
+ * (v_b - ret_b)^2:
+ *   loss_b = -min(rho_b adv_b, clamp(rho_b, 1 - eps_clip, 1 + eps_clip) adv_b) + vf_coef mse - ent_coef H_b
+ * (the reference: vf_coef = 0.5, ent_coef = 0.01); loss_abs_dev [B] = |loss_b|, loss_mean_dev [1]
+ * (nullable) = the mean of loss_b.  The backward of that mean goes into actor_grads[6] -- through
+ * d/d(logits) = (1/B) [k_b (onehot(a_b) - p_b) + ent_coef p_b (logp_b + H_b)], k_b = -rho_b adv_b
+ * where the unclipped term is the minimum or rho_b lies inside the clip range, else 0 -- and into
+ * value_grads[6] -- through d/dv_b = 2 vf_coef (v_b - ret_b) / B; the advantage carries no gradient.
+ * Both gradient arrays NULL: evaluate only (loss_abs, loss_mean and the workspace are written,
+ * nothing else); one of them NULL is an error.  Actions (int64) must lie in [0, A).  Afterwards
+ * the first B floats of the workspace hold the new log-probabilities logp_b[a_b] -- rth_ppo_act's
+ * logprob for that network, row and action, bit for bit.  Two launches: the tile pass, then the
+ * batch reductions in a fixed order (no atomics), which also finish the per-row loss. */
+int rth_ppo_grads(const float *const *actor, const float *const *value, const float *s_dev, int64_t lds,
+                  const int64_t *a_dev, const float *ret_dev, const float *old_logprob_dev, int64_t B, int64_t D,
+                  int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
+                  float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
+                  void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Device-resident continuous-control actors on DDPG's fused actor (csrc/ddpg_actor.hpp): one
  * launch per env step of N envs, one kernel templated on the env:
  *   RTH_DDPG_ENV_PENDULUM  Pendulum-v0  D = 3, Ad = 1, reward -cost, no terminal state

@@ -292,6 +292,14 @@ SIGNATURES = {
                                      c_i64, c_i64, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "rth_soft_update": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_f64,
                                 c_vp]),
+    # PPO's actor and value network (ppo.hpp)
+    "rth_ppo_supported": (c_i32, [c_i64, c_i64, c_i64]),
+    "rth_ppo_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "rth_ppo_act": (c_i32, [ctypes.POINTER(c_vp), c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_u64, c_u64, c_vp,
+                            c_vp, c_vp, c_vp]),
+    "rth_ppo_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64,
+                              c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp,
+                              c_vp, c_vp]),
     # the CartPole actors on the MLP kernels (mlp_actor.hpp: adapters onto the step below)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),
     "rth_mlp_actor_step": (c_i32, [c_vp, ctypes.POINTER(MlpActorArgs), c_vp]),

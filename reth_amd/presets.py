@@ -2,7 +2,7 @@
 
 Reference: reth/reth/presets/worker.py:12-163 (Worker), reth/reth/utils/exploration.py:16-53
 (RandomExploration; OUNoiseExploration lives in noise.py), reth/reth/presets/config.py:12-73 (get_env / get_solver / get_worker /
-get_trainer / get_replay_buffer).  The worker steps a host environment (the reference's
+get_trainer / get_replay_buffer; get_solver also resolves "ppo", to reth_amd.ppo.PPOSolver).  The worker steps a host environment (the reference's
 examples run one gym env per process); the solver, buffers and trainer are the device
 ones (DQNSolver, reth_amd.buffer, Trainer).
 """
@@ -148,10 +148,17 @@ def get_env(f, **kwargs):
 
 
 def get_solver(f, env=None, **kwargs):
+    """config.py:24-33.  solver: {name: ppo, ...} builds reth_amd.ppo.PPOSolver here; every other
+    name goes on to solver.get_solver"""
     config = _parse_input(f)
     env = env if env is not None else get_env(config)
-    return _get_solver(observation_space=env.observation_space, action_space=env.action_space,
-                       **{**config["solver"], **kwargs})
+    args = {**config["solver"], **kwargs}
+    if args.get("name") == "ppo":
+        from .ppo import PPOSolver
+
+        del args["name"]
+        return PPOSolver(observation_space=env.observation_space, action_space=env.action_space, **args)
+    return _get_solver(observation_space=env.observation_space, action_space=env.action_space, **args)
 
 
 def get_worker(f, solver=None, env=None, **kwargs):

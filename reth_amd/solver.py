@@ -423,7 +423,8 @@ class DQNSolver(Algorithm):
 
 def get_solver(name, **kwargs):
     """reth/reth/algorithm/__init__.py:17-21: "dqn" -> DQNSolver, "ddpg" -> DDPGSolver (ddpg.py);
-    the on-policy solvers (a2c, pg, ppo) are not rebuilt"""
+    the on-policy solvers (a2c, pg, ppo) are not resolved here.  PPO is rebuilt as
+    reth_amd.ppo.PPOSolver and resolved by the config-level presets.get_solver"""
     if name == "dqn":
         return DQNSolver(**kwargs)
     if name == "ddpg":

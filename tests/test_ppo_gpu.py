@@ -1,0 +1,479 @@
+"""rth_ppo_act / rth_ppo_grads (csrc/ppo.hpp) against fp64 on the CPU and against themselves
+(position independence, determinism, bounds), and PPOSolver's HIP path against the reference's
+recorded run, against its torch path and as a replayed graph.
+
+Shapes are (B, D, A) at H = 64.  Inputs: the reference's initialisation with the actor's last
+weight scaled by 4 (the probabilities spread), states and returns randn, actions sampled from the
+fp64 policy, and old log-probabilities logp64_b[a_b] - log rho_b with rho_b cycling through
+{0.5, 0.75, 0.9, 1.0, 1.1, 1.25, 1.6}: every ratio sits >= 0.05 from a clip bound (0.8, 1.2) by
+construction, so fp32 rounding flips no clip decision; the advantage's sign needs no margin, the
+loss and its gradient are continuous there.  For seeds 0..39 the first is taken at which, in fp64,
+min p >= 1e-4 (the reference's clamp of the probabilities to [1.19e-7, 1 - 1.19e-7] is inactive)
+and, for B >= 64, all six (below / inside / above the clip range) x (sign of the advantage) classes
+are present.
+
+The error bound is the project's: |ours - fp64| <= max(1.5 |torch fp32 CPU - fp64|, 1e-6 max|fp64|)
+per tensor, the reference in both precisions being the reference's expression (Categorical,
+torch.min, F.mse_loss) with autograd on the CPU."""
+import functools
+import os
+import runpy
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+from torch.distributions import Categorical
+
+from conftest import ROOT
+from reth_amd import _lib
+from reth_amd._lib import c_vp, call
+from reth_amd.ppo import ENT_COEF, VF_COEF, PPOSolver, _params6, generate_discrite_ppo_model
+from reth_amd.solver import Box, Discrete
+from test_ppo_cpu import ACT, NETS, OBS, golden_batch, golden_solver
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1, 2), (5, 4, 2), (64, 4, 2), (67, 7, 3), (130, 17, 6), (257, 64, 18), (8200, 4, 2)]
+H, EPS = 64, 0.2
+EPS32 = float(np.float32(EPS))
+RHO = [0.5, 0.75, 0.9, 1.0, 1.1, 1.25, 1.6]
+GRAD_NAMES = [f"{net}.{k}" for net in ("actor", "value") for k in ("0.w", "0.b", "2.w", "2.b", "4.w", "4.b")]
+
+
+def _nets(D, A, dtype=torch.float32, like=None):
+    """(actor, value), optionally copies of `like` in `dtype`"""
+    m = generate_discrite_ppo_model(Box(-1, 1, (D,)), Discrete(A), hidden_size=H)
+    nets = [m["actor_network"], m["value_network"]]
+    if like is not None:
+        for n, src in zip(nets, like):
+            n.to(dtype)
+            n.load_state_dict({k: v.to(dtype) for k, v in src.state_dict().items()})
+    return nets
+
+
+@functools.lru_cache(maxsize=None)
+def case(B, D, A):
+    """the first qualifying seed's networks and batch (CPU tensors; shared, never modified)"""
+    for seed in range(40):
+        torch.manual_seed(seed)
+        nets = _nets(D, A)
+        with torch.no_grad():
+            nets[0].action_layer[4].weight.mul_(4.0)
+        s, ret = torch.randn(B, D), torch.randn(B)
+        a64, v64 = _nets(D, A, torch.float64, nets)
+        with torch.no_grad():
+            p64 = a64(s.double())
+            adv = ret.double() - v64(s.double()).squeeze(-1)
+        g = torch.Generator().manual_seed(1000 + seed)
+        a = torch.multinomial(p64, 1, generator=g)[:, 0]
+        rho = torch.tensor(RHO, dtype=torch.float64)[torch.arange(B) % len(RHO)]
+        old = (p64.log().gather(1, a[:, None])[:, 0] - rho.log()).float()
+        if float(p64.min()) < 1e-4:
+            continue
+        where = torch.where(rho < 1 - EPS, 0, torch.where(rho > 1 + EPS, 2, 1)) * 2 + (adv > 0).long()
+        if B >= 64 and len(set(where.tolist())) != 6:
+            continue
+        return dict(seed=seed, shape=(B, D, A), nets=nets, s=s, a=a, ret=ret, old=old)
+    raise AssertionError(f"no qualifying seed in 0..39 for {(B, D, A)}")
+
+
+@functools.lru_cache(maxsize=None)
+def ref(shape, dtype):
+    """ppo_solver.py:53-96 with torch ops on the CPU in `dtype`: probs, the new log-probabilities,
+    |loss|, the loss mean and the twelve gradients (actor, then value).  Computed once per shape."""
+    c = case(*shape)
+    actor, value = _nets(*shape[1:], dtype, c["nets"])
+    s, ret, old = c["s"].to(dtype), c["ret"].to(dtype), c["old"].to(dtype)
+    probs = actor(s)
+    dist = Categorical(probs)
+    logp = dist.log_prob(c["a"])
+    v = torch.squeeze(value(s), -1)
+    ratios = torch.exp(logp - old)
+    adv = ret - v.detach()
+    rho = ratios.detach()
+    ratio_ok = float(torch.minimum((rho - (1 - EPS)).abs(), (rho - (1 + EPS)).abs()).min()) > 0.04
+    loss = (-torch.min(ratios * adv, torch.clamp(ratios, 1 - EPS, 1 + EPS) * adv) + VF_COEF * F.mse_loss(v, ret)
+            - ENT_COEF * dist.entropy())
+    loss.mean().backward()
+    grads = [p.grad for p in _params6(actor)] + [p.grad for p in _params6(value)]
+    return dict(probs=probs.detach(), logp_all=dist.logits.detach(), logp=logp.detach(), loss_abs=loss.detach().abs(),
+                loss_mean=loss.detach().mean(), grads=grads, ratio_ok=ratio_ok)
+
+
+def _arr(ts):
+    return (c_vp * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _params(c, dev):
+    return [[p.detach().to(dev).contiguous() for p in _params6(n)] for n in c["nets"]]
+
+
+def _ws(c, dev):
+    B, D, A = c["shape"]
+    return torch.empty(_lib.lib().rth_ppo_workspace(B, D, H, A) // 4, dtype=torch.float32, device=dev)
+
+
+def ppo_act(ps, x, D, A, uniforms=None, seed=0, counter=0, action=None, logprob=None, probs=None):
+    """rth_ppo_act over the rows of the (possibly row-strided) device matrix x -> (action, logprob, probs)"""
+    n = x.shape[0]
+    action = torch.full((n,), -7, dtype=torch.int64, device=x.device) if action is None else action
+    logprob = torch.full((n,), float("nan"), device=x.device) if logprob is None else logprob
+    probs = torch.full((n, A), float("nan"), device=x.device) if probs is None else probs
+    assert x.stride(1) == 1
+    call("rth_ppo_act", _arr(ps), x.data_ptr(), x.stride(0), n, D, H, A,
+         None if uniforms is None else uniforms.data_ptr(), seed, counter, action.data_ptr(), logprob.data_ptr(),
+         probs.data_ptr(), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return action, logprob, probs
+
+
+def ppo_grads(P, c, dev, backward=True, grads=None, loss_abs=None, loss_mean=None, s=None, ws=None):
+    """rth_ppo_grads on the case's batch -> (loss_abs, loss_mean, the twelve gradients, workspace)"""
+    B, D, A = c["shape"]
+    s = c["s"].to(dev) if s is None else s
+    a, ret, old = c["a"].to(dev), c["ret"].to(dev), c["old"].to(dev)
+    grads = [torch.full_like(p, float("nan")) for net in P for p in net] if grads is None else grads
+    loss_abs = torch.full((B,), float("nan"), device=dev) if loss_abs is None else loss_abs
+    loss_mean = torch.full((1,), float("nan"), device=dev) if loss_mean is None else loss_mean
+    ws = _ws(c, dev) if ws is None else ws
+    call("rth_ppo_grads", _arr(P[0]), _arr(P[1]), s.data_ptr(), s.stride(0), a.data_ptr(), ret.data_ptr(),
+         old.data_ptr(), B, D, H, A, EPS32, VF_COEF, ENT_COEF, _arr(grads[:6]) if backward else None,
+         _arr(grads[6:]) if backward else None, loss_abs.data_ptr(), loss_mean.data_ptr(), ws.data_ptr(),
+         _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return loss_abs, loss_mean, grads, ws
+
+
+def _check(label, ours, ref32, ref64, fails):
+    """the bound of the module docstring on one tensor"""
+    scale = float(ref64.abs().max())
+    e_ours = float((ours.cpu().double() - ref64).abs().max())
+    e_ref = float((ref32.double() - ref64).abs().max())
+    bound = max(1.5 * e_ref, 1e-6 * scale)
+    print(f"{label:44s} |ours - fp64| {e_ours:.3e}  |torch fp32 - fp64| {e_ref:.3e}  bound {bound:.3e}  "
+          f"max|fp64| {scale:.3e}")
+    if not e_ours <= bound:
+        fails.append((label, e_ours, e_ref, bound))
+
+
+def inverse_cdf(probs, u):
+    """the documented rule on the returned fp32 probabilities: the first j with (double) c_j > u"""
+    c = np.cumsum(probs.cpu().numpy(), axis=1, dtype=np.float32).astype(np.float64)
+    hit = c > u.cpu().numpy()[:, None]
+    return np.where(hit.any(1), hit.argmax(1), probs.shape[1] - 1)
+
+
+def uniforms_for(probs, actions):
+    """uniforms in the middle of each action's CDF interval"""
+    c = np.cumsum(probs.cpu().numpy(), axis=1, dtype=np.float32).astype(np.float64)
+    c = np.concatenate([np.zeros((c.shape[0], 1)), c], 1)
+    i = np.arange(c.shape[0])
+    a = actions.cpu().numpy()
+    return torch.as_tensor((c[i, a] + c[i, a + 1]) / 2, device=probs.device)
+
+
+# ------------------------------------------------------------------ 1. act against fp64
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_act_vs_fp64(dev, shape):
+    B, D, A = shape
+    c = case(*shape)
+    r64, r32 = ref(shape, torch.float64), ref(shape, torch.float32)
+    assert float(r64["probs"].min()) >= 1e-4 and r64["ratio_ok"]
+    u = torch.rand(B, dtype=torch.float64, generator=torch.Generator().manual_seed(5)).to(dev)
+    if B > 2:
+        u[0], u[1] = 0.0, 1.0 - 2.0 ** -53
+    action, logprob, probs = ppo_act(_params(c, dev)[0], c["s"].to(dev), D, A, uniforms=u)
+    fails = []
+    _check(f"probs {shape} seed {c['seed']}", probs, r32["probs"], r64["probs"], fails)
+    pick = lambda t: t.gather(1, action.cpu()[:, None])[:, 0]
+    _check(f"logprob {shape}", logprob, pick(r32["logp_all"]), pick(r64["logp_all"]), fails)
+    assert not fails, fails
+    assert np.array_equal(action.cpu().numpy(), inverse_cdf(probs, u))
+    assert torch.allclose(logprob.exp(), pick(probs.cpu()).to(dev), rtol=1e-6, atol=0)  # p_j = exp(logp_j)
+    if B > 2:
+        assert int(action[0]) == 0
+
+
+# ------------------------------------------------------------------ 2. position and stride
+def test_act_is_position_and_stride_independent(dev):
+    shape = (130, 17, 6)
+    B, D, A = shape
+    c = case(*shape)
+    ps, x = _params(c, dev)[0], c["s"].to(dev)
+    u = torch.rand(B, dtype=torch.float64, generator=torch.Generator().manual_seed(6)).to(dev)
+    out = ppo_act(ps, x, D, A, uniforms=u)
+    one = [ppo_act(ps, x[i:i + 1], D, A, uniforms=u[i:i + 1]) for i in range(B)]
+    flip = ppo_act(ps, x.flip(0).contiguous(), D, A, uniforms=u.flip(0).contiguous())
+    wide = torch.full((B, D + 3), 7.0, device=dev)
+    wide[:, :D] = x
+    assert wide[:, :D].stride(0) == D + 3
+    emb = ppo_act(ps, wide[:, :D], D, A, uniforms=u)
+    for k in range(3):
+        assert torch.equal(torch.cat([o[k] for o in one]), out[k])
+        assert torch.equal(flip[k].flip(0), out[k]) and torch.equal(emb[k], out[k])
+
+
+# ------------------------------------------------------------------ 3. the Philox path
+def test_philox_draws(dev):
+    shape = (67, 7, 3)
+    B, D, A = shape
+    c = case(*shape)
+    ps, x = _params(c, dev)[0], c["s"].to(dev)
+    a0, lp0, p0 = ppo_act(ps, x, D, A, seed=11, counter=3)
+    a1, lp1, p1 = ppo_act(ps, x, D, A, seed=11, counter=3)
+    a2, _, p2 = ppo_act(ps, x, D, A, seed=11, counter=4)
+    assert torch.equal(a0, a1) and torch.equal(lp0, lp1) and torch.equal(p0, p2)
+    assert not torch.equal(a0, a2) and int(a0.min()) >= 0 and int(a0.max()) < A
+    assert torch.allclose(lp0.exp(), p0.gather(1, a0[:, None])[:, 0], rtol=1e-6, atol=0)
+    n = 65536
+    many = x[3:4].expand(n, D).contiguous()
+    a, _, p = ppo_act(ps, many, D, A, seed=12345, counter=0)
+    assert bool((p == p[0]).all())
+    pj = p[0].double().cpu().numpy()
+    freq = np.bincount(a.cpu().numpy(), minlength=A) / n
+    print("p", pj, "freq", freq)
+    assert np.all(np.abs(freq - pj) <= 5 * np.sqrt(pj * (1 - pj) / n))
+
+
+# ------------------------------------------------------------------ 4. the gradients
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_grads_vs_fp64_autograd(dev, shape):
+    B, D, A = shape
+    c = case(*shape)
+    P = _params(c, dev)
+    r64, r32 = ref(shape, torch.float64), ref(shape, torch.float32)
+    assert float(r64["probs"].min()) >= 1e-4 and r64["ratio_ok"]
+    loss_abs, loss_mean, grads, ws = ppo_grads(P, c, dev)
+    fails = []
+    tag = f"{shape} seed {c['seed']} "
+    _check(tag + "|loss|", loss_abs, r32["loss_abs"], r64["loss_abs"], fails)
+    _check(tag + "loss mean", loss_mean.view(()), r32["loss_mean"], r64["loss_mean"], fails)
+    _check(tag + "new logp", ws[:B], r32["logp"], r64["logp"], fails)
+    for name, g, g32, g64 in zip(GRAD_NAMES, grads, r32["grads"], r64["grads"]):
+        assert g.shape == g64.shape
+        _check(tag + name, g, g32, g64, fails)
+    assert not fails, fails
+    # evaluate only: the same loss bit for bit, the gradient buffers left alone
+    keep = [torch.full_like(g, float("nan")) for g in grads]
+    la2, lm2, _, ws2 = ppo_grads(P, c, dev, backward=False, grads=keep)
+    assert torch.equal(la2, loss_abs) and torch.equal(lm2, loss_mean) and torch.equal(ws2[:B], ws[:B])
+    assert all(bool(torch.isnan(k).all()) for k in keep)
+    # the new log-probabilities are rth_ppo_act's for those actions, bit for bit
+    x = c["s"].to(dev)
+    _, _, probs = ppo_act(P[0], x, D, A, uniforms=torch.zeros(B, dtype=torch.float64, device=dev))
+    action, logprob, _ = ppo_act(P[0], x, D, A, uniforms=uniforms_for(probs, c["a"]))
+    assert torch.equal(action.cpu(), c["a"]) and torch.equal(logprob, ws[:B])
+    with pytest.raises(_lib.RethHipError, match="both gradient arrays or neither"):
+        call("rth_ppo_grads", _arr(P[0]), _arr(P[1]), x.data_ptr(), D, c["a"].to(dev).data_ptr(), x.data_ptr(),
+             x.data_ptr(), B, D, H, A, EPS32, VF_COEF, ENT_COEF, _arr(grads[:6]), None, loss_abs.data_ptr(), None,
+             ws.data_ptr(), _lib.stream_ptr())
+
+
+# ------------------------------------------------------------------ 5. bounds
+def test_nothing_outside_the_rows_columns_and_buffers_is_touched(dev):
+    shape = (67, 7, 3)
+    B, D, A = shape
+    PAD, S = 5, 12345.0
+    c = case(*shape)
+    P = _params(c, dev)
+    u = torch.rand(B, dtype=torch.float64, generator=torch.Generator().manual_seed(7)).to(dev)
+    la_c, lm_c, g_c, ws_c = ppo_grads(P, c, dev)  # outputs pre-filled with NaN
+    act_c = ppo_act(P[0], c["s"].to(dev), D, A, uniforms=u)
+    for t in [la_c, lm_c, *g_c, act_c[1], act_c[2]]:  # every output element is written
+        assert not bool(torch.isnan(t).any())
+    assert int(act_c[0].min()) >= 0
+    assert [tuple(g.shape) for g in g_c] == [(H, D), (H,), (H, H), (H,), (A, H), (A,), (H, D), (H,), (H, H), (H,),
+                                             (1, H), (1,)]
+    big = torch.full((B + 2 * PAD, D + 4), float("nan"), device=dev)  # NaN rows around and NaN columns beside
+    big[PAD:PAD + B, :D] = c["s"].to(dev)
+    s = big[PAD:PAD + B, :D]
+    nan = torch.isnan(big).clone()
+
+    def guarded(numel, dtype=torch.float32):
+        buf = torch.full((numel + 2 * 64,), S, device=dev).to(dtype)
+        return buf, buf[64:64 + numel]
+
+    gbig, grads = zip(*[guarded(g.numel()) for g in g_c])
+    grads = [g.view(r.shape) for g, r in zip(grads, g_c)]
+    labig, la = guarded(B)
+    lmbig, lm = guarded(1)
+    size = _lib.lib().rth_ppo_workspace(B, D, H, A) // 4
+    wbig, ws = guarded(size)
+    abig, action = guarded(B, torch.int64)
+    lbig, logprob = guarded(B)
+    pbig, probs = guarded(B * A)
+    ppo_grads(P, c, dev, grads=grads, loss_abs=la, loss_mean=lm, s=s, ws=ws)
+    ppo_act(P[0], s, D, A, uniforms=u, action=action, logprob=logprob, probs=probs.view(B, A))
+    checks = [(b, g.numel()) for b, g in zip(gbig, grads)]
+    for buf, n in checks + [(labig, B), (lmbig, 1), (wbig, size), (abig, B), (lbig, B), (pbig, B * A)]:
+        assert bool((buf[:64] == S).all()) and bool((buf[64 + n:] == S).all())
+    assert torch.equal(torch.isnan(big), nan)  # inputs unchanged
+    # ... and nothing read there: the results are those of the compact inputs, bit for bit
+    assert torch.equal(la, la_c) and torch.equal(lm, lm_c) and torch.equal(ws[:B], ws_c[:B])
+    assert all(torch.equal(x, y) for x, y in zip(grads, g_c))
+    assert torch.equal(action, act_c[0]) and torch.equal(logprob, act_c[1]) and torch.equal(probs.view(B, A), act_c[2])
+
+
+# ------------------------------------------------------------------ 6. determinism
+def test_twenty_repetitions_are_bit_identical(dev):
+    shape = (130, 17, 6)
+    B, D, A = shape
+    c = case(*shape)
+    P = _params(c, dev)
+    x = c["s"].to(dev)
+    first = None
+    for _ in range(20):
+        loss_abs, loss_mean, grads, ws = ppo_grads(P, c, dev)
+        out = [loss_abs, loss_mean, *grads, ws[:B].clone(), *ppo_act(P[0], x, D, A, seed=5, counter=9)]
+        if first is None:
+            first = out
+        assert all(torch.equal(x_, y_) for x_, y_ in zip(out, first))
+
+
+# ------------------------------------------------------------------ 7. unsupported shapes
+def test_unsupported_shape_is_an_error_and_launches_nothing(dev):
+    def run(D, Hh, A, ld):
+        actor = [torch.zeros(s, device=dev) for s in [(Hh, D), (Hh,), (Hh, Hh), (Hh,), (A, Hh), (A,)]]
+        value = [torch.zeros(s, device=dev) for s in [(Hh, D), (Hh,), (Hh, Hh), (Hh,), (1, Hh), (1,)]]
+        x, col = torch.zeros(3, D, device=dev), torch.zeros(3, device=dev)
+        a = torch.zeros(3, dtype=torch.int64, device=dev)
+        action = torch.full((3,), 5, dtype=torch.int64, device=dev)
+        full = lambda *shape: torch.full(shape, 5.0, device=dev)
+        outs = [full(3), full(3, A), full(3), full(1), full(3 * 1024)]  # logprob, probs, |loss|, loss mean, workspace
+        grads = [torch.full_like(p, 5.0) for p in actor + value]
+        sp = _lib.stream_ptr()
+        want = "unsupported shape.*H = 64, D in 1..64, A in 2..18" if ld >= D else f"{ld} < D={D}"
+        with pytest.raises(_lib.RethHipError, match=want):
+            call("rth_ppo_act", _arr(actor), x.data_ptr(), ld, 3, D, Hh, A, None, 1, 2, action.data_ptr(),
+                 outs[0].data_ptr(), outs[1].data_ptr(), sp)
+        with pytest.raises(_lib.RethHipError, match=want):
+            call("rth_ppo_grads", _arr(actor), _arr(value), x.data_ptr(), ld, a.data_ptr(), col.data_ptr(),
+                 col.data_ptr(), 3, D, Hh, A, EPS32, VF_COEF, ENT_COEF, _arr(grads[:6]), _arr(grads[6:]),
+                 outs[2].data_ptr(), outs[3].data_ptr(), outs[4].data_ptr(), sp)
+        torch.cuda.synchronize()
+        for t in [action, *outs, *grads]:
+            assert bool((t == 5).all())
+
+    run(4, 100, 2, 4)
+    run(4, 64, 19, 4)
+    run(4, 64, 2, 3)
+    assert _lib.lib().rth_ppo_supported(4, 100, 2) == 0 and _lib.lib().rth_ppo_supported(4, 64, 19) == 0
+
+
+# ------------------------------------------------------------------ 8. the solver
+def _close(label, got, want, drift, fails):
+    """max(5 x the golden's recorded fp32-vs-fp64 drift of the reference, 1e-6 max|value|) per tensor"""
+    got, want = torch.as_tensor(got).detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
+    err, bound = float((got - want).abs().max()), max(5 * drift, 1e-6 * float(want.abs().max()))
+    print(f"{label:40s} max difference {err:.3e}  bound {bound:.3e}")
+    if not err <= bound:
+        fails.append((label, err, bound))
+
+
+def test_solver_hip_against_the_golden_and_the_torch_path(dev, golden):
+    g = golden("ppo_cartpole_b64.npz")
+    dp, dl = float(g["drift_param"]), float(g["drift_loss"])
+    hip, tor = golden_solver(g, dev, impl="hip"), golden_solver(g, dev, impl="torch")
+    assert (hip.impl_active, tor.impl_active) == ("hip", "torch") and hip.hip_launches == 0
+    assert golden_solver(g, dev).impl_active == "hip"  # the default takes the kernels on a GPU
+    assert type(tor.actor_optimizer) is torch.optim.Adam
+    batch = [torch.as_tensor(x, device=dev) for x in golden_batch(g)]
+    fails = []
+    for k in range(3):
+        a, b = hip.update(batch), tor.update(batch)
+        assert a.shape == (64,) and a.dtype == torch.float32 and a.device.type == "cpu"
+        _close(f"update {k} |loss| hip vs golden", a, g[f"upd{k}_abs_loss"], dl, fails)
+        _close(f"update {k} |loss| hip vs torch", a, b, dl, fails)
+    assert hip.hip_launches == 3 * 3 * hip.k_epochs and hip.k_epochs == 4
+    for name, key, _ in NETS:
+        for (k, p), q in zip(getattr(hip, key).state_dict().items(), getattr(tor, key).state_dict().values()):
+            _close(f"final {name} {k} hip vs golden", p, g[f"final/{name}/{k}"], dp, fails)
+            _close(f"final {name} {k} hip vs torch", p, q, dp, fails)
+    # the probabilities are, like the loss, outputs of the updated networks: the loss's drift
+    x = torch.as_tensor(g["act_states"], device=dev)
+    u = torch.tensor([0.1, 0.6, 0.3, 0.9], dtype=torch.float64, device=dev)
+    ah, lh, ph = hip.act_batch(x, uniforms=u, return_probs=True)
+    at, lt, pt = tor.act_batch(x, uniforms=u, return_probs=True)
+    assert ah.dtype == torch.int64 and lh.dtype == torch.float32 and ah.device == lh.device == dev
+    _close("act_batch probs hip vs torch", ph, pt, dl, fails)
+    golden_actions = torch.as_tensor(g["act_actions"], device=dev)
+    _close("act_batch logprob vs golden", ph.log().gather(1, golden_actions[:, None])[:, 0], g["act_logprobs"], dl, fails)
+    assert torch.equal(ah, at) and torch.equal(ah.cpu(), torch.as_tensor(inverse_cdf(ph, u)))
+    assert torch.equal(lh, hip.act_batch(x, uniforms=u)[1])
+    a, lp = hip.act(g["act_states"][1])
+    assert type(a) is int and type(lp) is float and a in (0, 1)
+    assert hip.hip_launches == 36 + 3 and tor.hip_launches == 0
+    assert not fails, fails
+    # a seeded hip solver draws the same actions again
+    r1, r2 = golden_solver(g, dev, impl="hip"), golden_solver(g, dev, impl="hip")
+    many = torch.zeros(256, 4, device=dev)  # (a fresh network: both actions are likely)
+    d1, d2 = r1.act_batch(many)[0], r2.act_batch(many)[0]
+    assert r1.seed == r2.seed and torch.equal(d1, d2) and 0 < int(d1.sum()) < 256
+    assert not torch.equal(r1.act_batch(many)[0], d1) and r1.act_calls == 2  # the call counter moves the draws on
+
+
+# ------------------------------------------------------------------ 9. a captured update
+def test_captured_update_replays(dev, golden):
+    g = golden("ppo_cartpole_b64.npz")
+    eager, graph = golden_solver(g, dev, impl="hip"), golden_solver(g, dev, impl="hip")
+    batch = [torch.as_tensor(x, device=dev).contiguous() for x in golden_batch(g)]
+    for s in (eager, graph):  # one eager update each: every persistent buffer exists
+        s.update_device(batch)
+    torch.cuda.synchronize()
+    n0 = torch.cuda.memory_stats(dev)["allocation.all.allocated"]
+    loss = eager.update_device(batch)
+    assert torch.cuda.memory_stats(dev)["allocation.all.allocated"] == n0  # update_device allocates nothing
+    want = [loss.clone()] + [eager.update_device(batch).clone() for _ in range(2)]
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    cg = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        with torch.cuda.graph(cg, stream=stream):
+            out = graph.update_device(batch)
+    torch.cuda.current_stream().wait_stream(stream)
+    for k in range(3):
+        cg.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, want[k]), k
+    for key in ("actor_network", "value_network"):
+        for p, q in zip(getattr(graph, key).parameters(), getattr(eager, key).parameters()):
+            assert torch.equal(p, q), key
+    for a, b in ((graph.actor_optimizer, eager.actor_optimizer), (graph.value_optimizer, eager.value_optimizer)):
+        assert int(a._step) == int(b._step) == 4 * 4
+
+
+# ------------------------------------------------------------------ 10. an unsupported solver shape
+def test_solver_unsupported_shape(dev):
+    torch.manual_seed(5)
+    s = PPOSolver(OBS, ACT, hidden_size=100, device=dev)
+    assert s.impl is None and s.impl_active == "torch"
+    g = torch.Generator().manual_seed(6)
+    batch = [torch.randn(32, 4, generator=g), torch.randint(0, 2, (32,), generator=g), torch.randn(32, generator=g),
+             torch.full((32,), float(np.log(0.5)))]
+    loss = s.update(batch)
+    assert loss.shape == (32,) and bool(torch.isfinite(loss).all()) and s.hip_launches == 0
+    a, lp = s.act(np.zeros(4))
+    assert a in (0, 1) and lp < 0 and s.hip_launches == 0
+    with pytest.raises(ValueError, match="impl='hip'.*H = 64"):
+        PPOSolver(OBS, ACT, hidden_size=100, device=dev, impl="hip")
+    models = generate_discrite_ppo_model(OBS, ACT)
+    models["actor_network"].double()
+    with pytest.raises(ValueError, match="float32"):
+        PPOSolver(OBS, ACT, models=models, device=dev, impl="hip")
+
+
+# ------------------------------------------------------------------ 11. the example
+@pytest.mark.parametrize("impl", ["hip", "torch"])
+def test_example_runs_end_to_end(dev, impl, monkeypatch, capsys):
+    path = os.path.join(ROOT, "examples", "cartpole_ppo_hip.py")
+    monkeypatch.setattr(sys, "argv", [path, "--impl", impl, "--updates", "2", "--seed", "1"])
+    monkeypatch.setattr(sys, "path", list(sys.path))
+    runpy.run_path(path, run_name="__main__")
+    line = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("cartpole_ppo ")][-1]
+    fields = dict(f.split("=") for f in line.split()[1:])
+    assert fields["impl"] == impl and fields["updates"] == "2" and fields["seed"] == "1"
+    assert int(fields["env_steps"]) == 4000 and int(fields["episodes"]) >= 20
+    assert np.isfinite(float(fields["mean_len_last10"])) and 1 <= float(fields["mean_len_last10"]) <= 200
+    assert (int(fields["hip_launches"]) > 0) == (impl == "hip")
