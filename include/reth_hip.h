@@ -1032,6 +1032,77 @@ int rth_ppo_grads(const float *const *actor, const float *const *value, const fl
                   int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
                   float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
                   void *stream);
+/* rth_ppo_grads for a batch whose row count is known only on the device: B is the CAPACITY (the
+ * workspace is laid out for it: rth_ppo_workspace(B, ...); loss_abs_dev holds B floats) and the
+ * batch is the first n = min(n_dev[0], B) rows, read on the device.  Gradients, loss_abs[0, n),
+ * loss_mean and the workspace's log-probabilities equal rth_ppo_grads' with B = n on those rows bit
+ * for bit (one code path); rows at n and beyond are neither read nor written.  n = 0: every
+ * gradient element and loss_mean are written 0. */
+int rth_ppo_grads_n(const float *const *actor, const float *const *value, const float *s_dev, int64_t lds,
+                    const int64_t *a_dev, const float *ret_dev, const float *old_logprob_dev, int64_t B, int64_t D,
+                    int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
+                    float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
+                    const int64_t *n_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Device-resident PPO actors on the fused actor above (csrc/ppo_actor.hpp): the on-policy rollout
+ * of reth/examples/ppo/run.py for N envs of the classic-control family (RTH_ENV_*: CartPole
+ * D = 4, A = 2; Acrobot D = 6, A = 3; MountainCar D = 2, A = 3; H = 64), kept in HBM.
+ * Step, one launch: per env the acting forward and log-softmax (rth_ppo_act's probabilities, bit
+ * for bit), t = t_dev[i] + 1, one Categorical draw by rth_ppo_act's inverse CDF on u =
+ * uniforms_in[i] or the Philox uniform of (seed, counter = t, lane = i, stream word 13), or
+ * action_in[i]; logprob of the action taken; the env's fp64 dynamics, time limit and reset
+ * (csrc/env_actor.hpp); and the row (s0, a, r, done, logp) appended to the env's rollout segment:
+ * columns [N, cap, .] dense, fill[i] rows stored, the first complete[i] of them in finished
+ * episodes.  A full segment stores nothing and counts the row in dropped[i]; nothing is written
+ * outside a buffer.  complete is int32 [2, N]: the live slot of env i is gen[i] & 1 (the finish
+ * reads one slot of every env and zeroes the other of its own, then gen[i] += 1).
+ * No host synchronisation, no atomics; graph-capturable.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rth_ppo_actor_args {
+  const float *const *actor;  /* the actor: HOST array of six device pointers (the step only) */
+  int64_t env;                /* RTH_ENV_* */
+  int64_t D, H, A;            /* must be the env's D and A; H = 64 */
+  double *state;              /* [N, 4] fp64 env state; columns the env does not use stay 0 */
+  int32_t *ep_steps;          /* [N] steps of the running episode */
+  int64_t *t_dev;             /* [N] env steps taken (the Philox counter) */
+  int64_t *stats;             /* [N, 3] finished episodes, sum of their lengths, last length */
+  double *ret_stats;          /* [N, 3] fp64: running return, sum of finished returns, last finished return */
+  float *cur_obs;             /* [N, LD] f32, LD = D rounded up to 4 (pad floats 0), 16-byte aligned: the
+                                 observation each env acts on next */
+  const int64_t *action_in;   /* [N] nullable: overrides the drawn action */
+  const double *uniforms_in;  /* [N] nullable: replaces the Philox uniform (double in [0, 1)) */
+  int64_t *action;            /* out [N]: the step's action */
+  float *logprob;             /* out [N]: its log-probability */
+  float *seg_s;               /* [N, cap, D] the observations acted on */
+  int64_t *seg_a;             /* [N, cap] */
+  float *seg_r, *seg_done, *seg_logp; /* [N, cap] each */
+  int32_t *fill;              /* [N] rows stored */
+  int32_t *complete;          /* [2, N] rows of finished episodes; env i's live slot: gen[i] & 1 */
+  int32_t *gen;               /* [N] finishes so far */
+  int64_t *dropped;           /* [N] rows not stored because the segment was full */
+  uint64_t seed;
+  int64_t N;
+  int32_t cap;                /* rows per env, 1..4096 */
+  int32_t max_episode_steps;  /* TimeLimit */
+} rth_ppo_actor_args;
+/* env.reset() of every env: states from Philox(seed, env, t = 0), ep_steps / t_dev / stats /
+ * ret_stats / fill / complete / gen / dropped = 0, the observation into cur_obs.  Arguments are
+ * checked before anything is launched (RTH_ERR_INVALID, rth_last_error). */
+int rth_ppo_env_reset(const rth_ppo_actor_args *args, void *stream);
+/* One env step of all N actors, one launch.  Arguments are checked before anything is launched. */
+int rth_ppo_actor_step(const rth_ppo_actor_args *args, void *stream);
+/* The end of a rollout, one launch, one workgroup per env.  Rows [0, complete[i]) of env i are whole
+ * episodes; each episode's returns are algorithm/util.py:27-40 on that episode alone, in fp64:
+ * backwards, run = run * gamma + r_t (one product, one sum), d_t = (float) run, a done row 0; then
+ * ret_t = (float) ((d_t - mean) / (sqrt(var) + 1e-7)) with the episode's own mean and population
+ * variance of the fp32 d_t, summed in increasing t.  The rows (s, a, ret, logp) go to the dense
+ * batch (batch_s [., D], the others [.]; N * cap rows hold any rollout) env-major, then in time
+ * order, n_dev[0] = their count; batch rows at n and beyond are left as they were.  The rows of
+ * the episode still running move to the front of the segment with their old log-probabilities:
+ * fill[i] -= complete[i], complete[i] = 0.  Arguments are checked before anything is launched. */
+int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *batch_s_dev, int64_t *batch_a_dev,
+                           float *batch_ret_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-resident continuous-control actors on DDPG's fused actor (csrc/ddpg_actor.hpp): one

@@ -9,6 +9,9 @@ include/reth_hip.h).  Modules mirror the reference's interfaces:
     reth_amd.ddpg          DDPGSolver (reth.algorithm.DDPGSolver), Actor, Critic
     reth_amd.ddpg_actors   VecDdpgActors (the DDPG worker loop with OU noise, vectorised on the GPU)
     reth_amd.ddpg_apex     DdpgApex / DdpgApexConfig (examples/ddpg wiring on one stream)
+    reth_amd.ppo           PPOSolver (reth.algorithm.PPOSolver), ActorNetwork, ValueNetwork
+    reth_amd.ppo_actors    VecPpoActors (the PPO rollout with its returns, vectorised on the GPU), HostRollout
+    reth_amd.ppo_loop      PpoLoop / PpoLoopConfig (examples/ppo wiring on one stream)
     reth_amd.device_loop   OneStreamLoop / VecEnvActors (what the 1-D device loops and actor sets share)
     reth_amd.trainer       Trainer (reth.presets.Trainer)
     reth_amd.actors        VecActors (the apex-dqn worker loop, vectorised on the GPU)

@@ -113,6 +113,16 @@ class EnvActorArgs(ctypes.Structure):
                 ("max_episode_steps", c_i32)]
 
 
+class PpoActorArgs(ctypes.Structure):
+    """rth_ppo_actor_args"""
+    _fields_ = [("actor", ctypes.POINTER(c_vp)), ("env", c_i64), ("D", c_i64), ("H", c_i64), ("A", c_i64),
+                ("state", c_vp), ("ep_steps", c_vp), ("t_dev", c_vp), ("stats", c_vp), ("ret_stats", c_vp),
+                ("cur_obs", c_vp), ("action_in", c_vp), ("uniforms_in", c_vp), ("action", c_vp), ("logprob", c_vp),
+                ("seg_s", c_vp), ("seg_a", c_vp), ("seg_r", c_vp), ("seg_done", c_vp), ("seg_logp", c_vp),
+                ("fill", c_vp), ("complete", c_vp), ("gen", c_vp), ("dropped", c_vp), ("seed", c_u64), ("N", c_i64),
+                ("cap", c_i32), ("max_episode_steps", c_i32)]
+
+
 DDPG_ENV_PENDULUM = 0  # RTH_DDPG_ENV_*
 
 
@@ -300,6 +310,13 @@ SIGNATURES = {
     "rth_ppo_grads": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64,
                               c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp,
                               c_vp, c_vp]),
+    "rth_ppo_grads_n": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # the PPO actors, their rollout and its end (ppo_actor.hpp)
+    "rth_ppo_env_reset": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),
+    "rth_ppo_actor_step": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),
+    "rth_ppo_rollout_finish": (c_i32, [ctypes.POINTER(PpoActorArgs), c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # the CartPole actors on the MLP kernels (mlp_actor.hpp: adapters onto the step below)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),
     "rth_mlp_actor_step": (c_i32, [c_vp, ctypes.POINTER(MlpActorArgs), c_vp]),

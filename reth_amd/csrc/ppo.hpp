@@ -79,6 +79,13 @@ struct PpoWs {
   static int64_t floats(int64_t B, int64_t A) { return B * (4 + A + 8 * kPpoH); }
 };
 
+// the rows of a batch of capacity `cap`: all of them, or the device's count n_dev[0] clamped to [0, cap]
+__device__ __forceinline__ int64_t ppo_rows(int64_t cap, const int64_t *__restrict__ n_dev) {
+  if (!n_dev) return cap;
+  const int64_t n = *n_dev;
+  return n < 0 ? 0 : (n < cap ? n : cap);
+}
+
 // a network's parameters (N3 rows in its last layer) into LDS; the caller synchronises before they are read
 __device__ inline void ppo_stage_net(const DenseNet &p, int D, int N3, PpoNetSmem &s) {
   const int tid = threadIdx.x;
@@ -190,6 +197,17 @@ __device__ inline void ppo_load_tile(const float *__restrict__ x, int64_t ldx, i
   dense_load_x(x, ldx, n, r0, D, xs);
 }
 
+// The Categorical draw, the only one: the inverse CDF over the running fp32 sum of a row's
+// probabilities -- the first j with c_j > u, c_j = fl32(c_{j-1} + p_j), or A - 1 if there is none
+__device__ __forceinline__ int ppo_inverse_cdf(const float *p, int A, double u) {
+  float c = 0.0f;
+  for (int j = 0; j < A; ++j) {
+    c = radd(c, p[j]);
+    if ((double)c > u) return j;
+  }
+  return A - 1;
+}
+
 __global__ __launch_bounds__(kPpoThreads) void k_ppo_act(DenseNet p, const float *__restrict__ x, int64_t ldx,
                                                          int64_t n, int D, int A, const double *__restrict__ uniforms,
                                                          uint64_t seed, uint64_t counter, int64_t *__restrict__ action,
@@ -203,18 +221,10 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_act(DenseNet p, const float
     ppo_load_tile(x, ldx, n, r0, D, s.x);
     ppo_forward_rows(s.actor, s.x, D, A, s.ra);
     ppo_log_softmax(s.ra.z, A, s.dist);
-    if (tid < kPpoRows && r0 + tid < n) {  // the inverse CDF: the first j with c_j > u, c_j = fl32(c_{j-1} + p_j)
+    if (tid < kPpoRows && r0 + tid < n) {
       const int64_t row = r0 + tid;
       const double u = uniforms ? uniforms[row] : philox_uniform(seed, counter, (uint32_t)row, STREAM_PPO);
-      float c = 0.0f;
-      int a = A - 1;
-      for (int j = 0; j < A; ++j) {
-        c = radd(c, s.dist.p[tid][j]);
-        if ((double)c > u) {
-          a = j;
-          break;
-        }
-      }
+      const int a = ppo_inverse_cdf(s.dist.p[tid], A, u);
       action[row] = a;
       logprob[row] = s.dist.logp[tid][a];
     }
@@ -264,16 +274,20 @@ __device__ inline void ppo_dgrad_store(const PpoNetSmem &w, const PpoRows &o, fl
 // entropy, the squared value error -- and, backward, d(mean loss)/d(logits), d/d(value) and both
 // networks' data gradients; activations and pre-activation gradients go to the workspace for the
 // second launch, which also finishes the per-row loss (the mean squared error is a batch scalar).
+// `cap` lays the workspace out; the batch is its first ppo_rows(cap, n_dev) rows.
 __global__ __launch_bounds__(kPpoThreads) void k_ppo_tile(DenseNet ac, DenseNet va, const float *__restrict__ st,
                                                           int64_t lds, const int64_t *__restrict__ act,
                                                           const float *__restrict__ ret,
-                                                          const float *__restrict__ old_logp, int64_t B, int D, int A,
+                                                          const float *__restrict__ old_logp, int64_t cap,
+                                                          const int64_t *__restrict__ n_dev, int D, int A,
                                                           float clip_lo, float clip_hi, float vf_coef, float ent_coef,
                                                           int backward, float *__restrict__ wsp) {
   __shared__ __align__(16) PpoGradSmem s;
-  const PpoWs ws(wsp, B, A);
+  const PpoWs ws(wsp, cap, A);
+  const int64_t B = ppo_rows(cap, n_dev);
   const int tid = threadIdx.x, j = tid & (kPpoH - 1), rb = (tid >> 6) * kPpoRpt;
   const int64_t tiles = (B + kPpoRows - 1) / kPpoRows;
+  if ((int64_t)blockIdx.x >= tiles) return;  // (uniform) no tile: nothing to stage the weights for
   const float invB = 1.0f / (float)B;
   ppo_stage_net(ac, D, A, s.actor);
   ppo_stage_net(va, D, 1, s.value);
@@ -348,11 +362,13 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_tile(DenseNet ac, DenseNet 
 // order (a chain of 32), and the chunks' sums are added in increasing order in fp64 and rounded
 // once; B <= kPpoChunk is dense.hpp's order itself.  A lane reads back only what it wrote itself
 // (the chunk's sum, parked in the gradient element it finally overwrites): no barrier, no atomics.
+// B = 0 (a device-counted batch without rows) writes zeros.
 constexpr int kPpoChunk = 128;
 
 __device__ inline void ppo_wgrad_tile(const float *__restrict__ G, int64_t ldg, int N, const float *__restrict__ X,
                                       int64_t ldx, int K, int64_t B, int n0, float *gw) {
   const int k = (int)threadIdx.x;
+  if (B == 0) return dense_wgrad_tile(G, ldg, N, X, ldx, K, 0, n0, 0, gw);
   double acc[kDenseGradJ] = {};
   for (int64_t c0 = 0; c0 < B; c0 += kPpoChunk) {
     const int64_t nb = B - c0 < kPpoChunk ? B - c0 : kPpoChunk;
@@ -370,6 +386,7 @@ __device__ inline void ppo_wgrad_tile(const float *__restrict__ G, int64_t ldg, 
 
 __device__ inline void ppo_bgrad(const float *__restrict__ G, int64_t ldg, int N, int64_t B, float *gb) {
   const int n = (int)threadIdx.x;
+  if (B == 0) return dense_bgrad(G, ldg, N, 0, 0, gb);
   double acc = 0.0;
   for (int64_t c0 = 0; c0 < B; c0 += kPpoChunk) {
     const int64_t nb = B - c0 < kPpoChunk ? B - c0 : kPpoChunk;
@@ -403,19 +420,22 @@ __device__ inline void ppo_net_wgrad(int blk, const DenseGrads &g, const float *
 // rth_ppo_grads' second launch: the batch reductions of both networks, then the loss workgroup:
 // mse = (1/B) sum_b (v_b - ret_b)^2, loss_b = le_b + vf_coef mse, |loss_b| and the mean of loss_b
 // as (1/B) sum_b le_b + vf_coef mse.  Without gradients only the loss workgroup runs (first = its index).
+// B = ppo_rows(cap, n_dev) as in the first launch; B = 0: zero gradients and a zero loss mean.
 __global__ __launch_bounds__(kDenseGradThreads) void k_ppo_wgrad(DenseGrads ga, DenseGrads gv,
-                                                                const float *__restrict__ st, int64_t lds, int64_t B,
-                                                                int D, int A, float vf_coef, float *__restrict__ wsp,
+                                                                const float *__restrict__ st, int64_t lds, int64_t cap,
+                                                                const int64_t *__restrict__ n_dev, int D, int A,
+                                                                float vf_coef, float *__restrict__ wsp,
                                                                 float *__restrict__ loss_abs,
                                                                 float *__restrict__ loss_mean, int first) {
   __shared__ float part[kDenseGradThreads];
-  const PpoWs ws(wsp, B, A);
+  const PpoWs ws(wsp, cap, A);
+  const int64_t B = ppo_rows(cap, n_dev);
   int blk = (int)blockIdx.x + first;
   const int na = ppo_net_blocks(A), nv = ppo_net_blocks(1);
   if (blk < na) return ppo_net_wgrad(blk, ga, st, lds, B, D, A, ws.ah1, ws.ah2, ws.ag1, ws.ag2, ws.g3);
   blk -= na;
   if (blk < nv) return ppo_net_wgrad(blk, gv, st, lds, B, D, 1, ws.vh1, ws.vh2, ws.vg1, ws.vg2, ws.gv);
-  const float invB = 1.0f / (float)B;
+  const float invB = B ? 1.0f / (float)B : 0.0f;
   const float vmse = rmul(vf_coef, rmul(dense_loss_sum(ws.se, B, part), invB));
   __syncthreads();  // every lane has read the sum before `part` is used again
   for (int64_t b = threadIdx.x; b < B; b += kDenseGradThreads) loss_abs[b] = fabsf(radd(ws.le[b], vmse));
@@ -431,6 +451,47 @@ inline bool ppo_shape_ok(int64_t D, int64_t H, int64_t A) {
 #define RTH_PPO_SHAPE(fn)                                                                              \
   RTH_REQUIRE(ppo_shape_ok(D, H, A), fn ": unsupported shape D=%lld H=%lld A=%lld " RTH_PPO_LIMITS, \
               (long long)D, (long long)H, (long long)A)
+
+// The body of rth_ppo_grads (n_dev = NULL: the batch is B rows) and rth_ppo_grads_n (B is the
+// capacity, the batch is the first min(*n_dev, B) rows): one code path.  The workspace is laid out
+// for B in both, and the chunks of kPpoChunk rows start at row 0 in both, so n rows out of a larger
+// capacity give what B = n gives, bit for bit.
+inline int ppo_grads_run(const char *fn, const float *const *actor, const float *const *value, const float *s_dev,
+                         int64_t lds, const int64_t *a_dev, const float *ret_dev, const float *old_logprob_dev,
+                         int64_t B, const int64_t *n_dev, int64_t D, int64_t H, int64_t A, float eps_clip,
+                         float vf_coef, float ent_coef, float *const *actor_grads, float *const *value_grads,
+                         float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev, void *stream) {
+  RTH_REQUIRE(ppo_shape_ok(D, H, A), "%s: unsupported shape D=%lld H=%lld A=%lld " RTH_PPO_LIMITS, fn, (long long)D,
+              (long long)H, (long long)A);
+  RTH_REQUIRE(B >= 1 && B <= (int64_t)1 << 40 && lds >= D, "%s: bad B=%lld or row stride %lld < D=%lld", fn,
+              (long long)B, (long long)lds, (long long)D);
+  DenseNet ac, va;
+  RTH_REQUIRE(dense_net(actor, &ac) && dense_net(value, &va) && s_dev && a_dev && ret_dev && old_logprob_dev &&
+                  loss_abs_dev && workspace_dev,
+              "%s: NULL argument", fn);
+  RTH_REQUIRE((actor_grads == nullptr) == (value_grads == nullptr),
+              "%s: both gradient arrays or neither (evaluate only)", fn);
+  const bool backward = actor_grads != nullptr;
+  DenseGrads ga{}, gv{};
+  if (backward) {
+    for (int i = 0; i < 6; ++i) RTH_REQUIRE(actor_grads[i] && value_grads[i], "%s: NULL gradient buffer %d", fn, i);
+    ga = DenseGrads{actor_grads[0], actor_grads[1], actor_grads[2], actor_grads[3], actor_grads[4], actor_grads[5]};
+    gv = DenseGrads{value_grads[0], value_grads[1], value_grads[2], value_grads[3], value_grads[4], value_grads[5]};
+  }
+  // the clip range as the reference's python floats 1 - eps and 1 + eps, rounded to fp32 once
+  const float lo = (float)(1.0 - (double)eps_clip), hi = (float)(1.0 + (double)eps_clip);
+  float *ws = static_cast<float *>(workspace_dev);
+  hipLaunchKernelGGL(k_ppo_tile, dim3(dense_grid(B)), dim3(kPpoThreads), 0, as_stream(stream), ac, va, s_dev, lds,
+                     a_dev, ret_dev, old_logprob_dev, B, n_dev, (int)D, (int)A, lo, hi, vf_coef, ent_coef,
+                     (int)backward, ws);
+  RTH_LAUNCHED();
+  const int grad_blocks = ppo_net_blocks((int)A) + ppo_net_blocks(1);
+  hipLaunchKernelGGL(k_ppo_wgrad, dim3(backward ? grad_blocks + 1 : 1), dim3(kDenseGradThreads), 0, as_stream(stream),
+                     ga, gv, s_dev, lds, B, n_dev, (int)D, (int)A, vf_coef, ws, loss_abs_dev, loss_mean_dev,
+                     backward ? 0 : grad_blocks);
+  RTH_LAUNCHED();
+  return RTH_OK;
+}
 
 }  // namespace rth
 
@@ -466,36 +527,20 @@ int rth_ppo_grads(const float *const *actor, const float *const *value, const fl
                   int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
                   float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
                   void *stream) {
-  using namespace rth;
-  RTH_PPO_SHAPE("rth_ppo_grads");
-  RTH_REQUIRE(B >= 1 && B <= (int64_t)1 << 40 && lds >= D, "rth_ppo_grads: bad B=%lld or row stride %lld < D=%lld",
-              (long long)B, (long long)lds, (long long)D);
-  DenseNet ac, va;
-  RTH_REQUIRE(dense_net(actor, &ac) && dense_net(value, &va) && s_dev && a_dev && ret_dev && old_logprob_dev &&
-                  loss_abs_dev && workspace_dev,
-              "rth_ppo_grads: NULL argument");
-  RTH_REQUIRE((actor_grads == nullptr) == (value_grads == nullptr),
-              "rth_ppo_grads: both gradient arrays or neither (evaluate only)");
-  const bool backward = actor_grads != nullptr;
-  DenseGrads ga{}, gv{};
-  if (backward) {
-    for (int i = 0; i < 6; ++i)
-      RTH_REQUIRE(actor_grads[i] && value_grads[i], "rth_ppo_grads: NULL gradient buffer %d", i);
-    ga = DenseGrads{actor_grads[0], actor_grads[1], actor_grads[2], actor_grads[3], actor_grads[4], actor_grads[5]};
-    gv = DenseGrads{value_grads[0], value_grads[1], value_grads[2], value_grads[3], value_grads[4], value_grads[5]};
-  }
-  // the clip range as the reference's python floats 1 - eps and 1 + eps, rounded to fp32 once
-  const float lo = (float)(1.0 - (double)eps_clip), hi = (float)(1.0 + (double)eps_clip);
-  float *ws = static_cast<float *>(workspace_dev);
-  hipLaunchKernelGGL(k_ppo_tile, dim3(dense_grid(B)), dim3(kPpoThreads), 0, as_stream(stream), ac, va, s_dev, lds,
-                     a_dev, ret_dev, old_logprob_dev, B, (int)D, (int)A, lo, hi, vf_coef, ent_coef, (int)backward, ws);
-  RTH_LAUNCHED();
-  const int grad_blocks = ppo_net_blocks((int)A) + ppo_net_blocks(1);
-  hipLaunchKernelGGL(k_ppo_wgrad, dim3(backward ? grad_blocks + 1 : 1), dim3(kDenseGradThreads), 0, as_stream(stream),
-                     ga, gv, s_dev, lds, B, (int)D, (int)A, vf_coef, ws, loss_abs_dev, loss_mean_dev,
-                     backward ? 0 : grad_blocks);
-  RTH_LAUNCHED();
-  return RTH_OK;
+  return rth::ppo_grads_run("rth_ppo_grads", actor, value, s_dev, lds, a_dev, ret_dev, old_logprob_dev, B, nullptr, D,
+                            H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
+                            workspace_dev, stream);
+}
+
+int rth_ppo_grads_n(const float *const *actor, const float *const *value, const float *s_dev, int64_t lds,
+                    const int64_t *a_dev, const float *ret_dev, const float *old_logprob_dev, int64_t B, int64_t D,
+                    int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
+                    float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
+                    const int64_t *n_dev, void *stream) {
+  RTH_REQUIRE(n_dev, "rth_ppo_grads_n: NULL row count");
+  return rth::ppo_grads_run("rth_ppo_grads_n", actor, value, s_dev, lds, a_dev, ret_dev, old_logprob_dev, B, n_dev, D,
+                            H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
+                            workspace_dev, stream);
 }
 
 }  // extern "C"

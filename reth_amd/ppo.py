@@ -227,7 +227,7 @@ class PPOSolver(Algorithm):
         x = self._tensor(x, torch.float32).reshape(-1, cols)
         return x if x.stride(1) == 1 and x.stride(0) >= cols else x.contiguous()
 
-    def _hip_update(self, batch):
+    def _hip_update(self, batch, n_rows=None):
         states, actions, returns, logprobs = batch
         D, H, A = self.dims
         s = self._matrix(states, D)
@@ -237,12 +237,16 @@ class PPOSolver(Algorithm):
         B = s.shape[0]
         if a.numel() != B or ret.numel() != B or old.numel() != B:
             raise ValueError("batch columns disagree in length")
+        if n_rows is not None and not (torch.is_tensor(n_rows) and n_rows.device == self.device
+                                       and n_rows.dtype == torch.int64 and n_rows.numel() == 1):
+            raise ValueError("n_rows: an int64 tensor [1] on the solver's device")
         ws, loss_abs, loss_mean = self._buffers(B)
+        fn, count = ("rth_ppo_grads", ()) if n_rows is None else ("rth_ppo_grads_n", (ptr(n_rows),))
         for _ in range(self.k_epochs):
             p = self._arrays()
-            call("rth_ppo_grads", p["actor"], p["value"], ptr(s), s.stride(0), ptr(a), ptr(ret), ptr(old), B, D, H, A,
+            call(fn, p["actor"], p["value"], ptr(s), s.stride(0), ptr(a), ptr(ret), ptr(old), B, D, H, A,
                  float(self.eps_clip), VF_COEF, ENT_COEF, p["actor_grads"], p["value_grads"], ptr(loss_abs),
-                 ptr(loss_mean), ptr(ws), stream_ptr())
+                 ptr(loss_mean), ptr(ws), *count, stream_ptr())
             self.actor_optimizer.step()
             self.value_optimizer.step()
             self.hip_launches += 3
@@ -292,12 +296,18 @@ class PPOSolver(Algorithm):
         return loss.detach().abs()
 
     # ------------------------------------------------------------------ public
-    def update_device(self, batch, weights=None):
+    def update_device(self, batch, weights=None, n_rows=None):
         """ppo_solver.py:63-100 on batch = (states, actions, returns, old log-probabilities): k_epochs
         full-batch epochs; the last epoch's |loss| [B] on the device, no host synchronisation
-        (weights is accepted and ignored, as in the reference)"""
+        (weights is accepted and ignored, as in the reference).  n_rows (a device int64 [1]): the
+        batch is the first min(n_rows, B) rows of the columns, counted on the device
+        (rth_ppo_grads_n; buffers are kept per capacity B, and |loss| beyond the count is stale).
+        The torch path reads n_rows on the host and slices: the yardstick only."""
         if self.impl_active == "hip":
-            return self._hip_update(batch)
+            return self._hip_update(batch, n_rows)
+        if n_rows is not None:
+            n = int(n_rows)
+            batch = [b[:n] for b in batch]
         return self._torch_update(batch)
 
     def update(self, batch, weights=None):
