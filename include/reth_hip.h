@@ -774,6 +774,15 @@ int rth_atari_synth_reset(uint8_t *reset_raw_dev, int64_t n, int64_t frame_bytes
  * the device; workspace_dev holds rth_clip_adam_workspace() bytes, zero-filled once before the
  * first call; one workspace per optimizer.  total_norm_out_dev (nullable) receives the pre-clip
  * 2-norm (clip_grad_norm_'s return).
+ * Every tensor has 1 <= n < 2^29 elements (n * 4 bytes is the 32-bit record count of the buffer
+ * resource the kernels read it through); rth_clip_adam and rth_adam_prenormed return
+ * RTH_ERR_INVALID for a larger one and launch nothing.
+ * Workspace layout: [32,768 doubles: the norm partials, summed in index order]
+ * [16 B: float coef, step_size, bc2_sqrt, total_norm -- the last update's scalars, written by the
+ * update] [8 B: float step_size, bc2_sqrt -- the bias corrections lr / (1 - beta1^t) and
+ * sqrt(1 - beta2^t) of step t, written with the step count and read by the update] [the rest
+ * unused].  A caller of rth_adam_prenormed fills the first nparts partials and the bias
+ * corrections; rth_adam_prenormed does not advance step_dev.
  * ---------------------------------------------------------------------------------- */
 #define RTH_MAX_PARAM_TENSORS 32
 typedef struct rth_param_tensor {

@@ -149,21 +149,27 @@ extern "C" {
 // (k_grad_sqsum -> k_adam, 8 B)]
 int64_t rth_clip_adam_workspace(void) { return (int64_t)kMaxPartials * 8 + 64; }
 
-static int adam_launch(const rth_param_tensor *tensors, int32_t n_tensors, double lr, double beta1, double beta2,
-                       double eps, double max_norm, int64_t *step_dev, void *workspace_dev, float *total_norm_out,
-                       int nparts, bool sqsum, hipStream_t s) {
-  RTH_REQUIRE(tensors && step_dev && workspace_dev, "rth_clip_adam: NULL argument");
-  RTH_REQUIRE(n_tensors >= 1 && n_tensors <= RTH_MAX_PARAM_TENSORS, "rth_clip_adam: %d tensors not in [1, %d]",
-              n_tensors, RTH_MAX_PARAM_TENSORS);
-  for (int i = 0; i < n_tensors; ++i)
+// a tensor's byte count must fit the buffer resource's 32-bit record count (seg_rsrc: n * 4) and
+// ld4b's 32-bit byte offset
+constexpr int64_t kMaxTensorElems = (int64_t)1 << 29;
+
+static int adam_launch(const char *who, const rth_param_tensor *tensors, int32_t n_tensors, double lr, double beta1,
+                       double beta2, double eps, double max_norm, int64_t *step_dev, void *workspace_dev,
+                       float *total_norm_out, int nparts, bool sqsum, hipStream_t s) {
+  RTH_REQUIRE(tensors && step_dev && workspace_dev, "%s: NULL argument", who);
+  RTH_REQUIRE(n_tensors >= 1 && n_tensors <= RTH_MAX_PARAM_TENSORS, "%s: %d tensors not in [1, %d]", who, n_tensors,
+              RTH_MAX_PARAM_TENSORS);
+  for (int i = 0; i < n_tensors; ++i) {
     RTH_REQUIRE(tensors[i].param && tensors[i].grad && tensors[i].exp_avg && tensors[i].exp_avg_sq && tensors[i].n >= 1,
-                "rth_clip_adam: tensor %d incomplete", i);
+                "%s: tensor %d incomplete", who, i);
+    RTH_REQUIRE(tensors[i].n < kMaxTensorElems, "%s: tensor %d has %lld elements (fewer than 2^29 = %lld)", who, i,
+                (long long)tensors[i].n, (long long)kMaxTensorElems);
+  }
   OptArgs a{}, ad{};
   const int64_t blocks = opt_segments(tensors, n_tensors, kOptChunk, &a);
   const int64_t ablocks = opt_segments(tensors, n_tensors, kAdamChunk, &ad);  // the same segments at k_adam's chunk
   if (sqsum) nparts = (int)(blocks < kMaxPartials ? blocks : kMaxPartials + 1);
-  RTH_REQUIRE(nparts >= 1 && nparts <= kMaxPartials, "rth_clip_adam: %d norm partials (at most %d)", nparts,
-              kMaxPartials);
+  RTH_REQUIRE(nparts >= 1 && nparts <= kMaxPartials, "%s: %d norm partials (at most %d)", who, nparts, kMaxPartials);
   auto *part = static_cast<double *>(workspace_dev);
   auto *sc = reinterpret_cast<OptScalars *>(static_cast<uint8_t *>(workspace_dev) + (int64_t)kMaxPartials * 8);
   const int clip = max_norm >= 0.0;
@@ -186,15 +192,15 @@ static int adam_launch(const rth_param_tensor *tensors, int32_t n_tensors, doubl
 int rth_clip_adam(const rth_param_tensor *tensors, int32_t n_tensors, double lr, double beta1, double beta2,
                   double eps, double max_norm, int64_t *step_dev, void *workspace_dev, float *total_norm_out,
                   void *stream) {
-  return adam_launch(tensors, n_tensors, lr, beta1, beta2, eps, max_norm, step_dev, workspace_dev, total_norm_out, 0,
-                     true, as_stream(stream));
+  return adam_launch("rth_clip_adam", tensors, n_tensors, lr, beta1, beta2, eps, max_norm, step_dev, workspace_dev,
+                     total_norm_out, 0, true, as_stream(stream));
 }
 
 int rth_adam_prenormed(const rth_param_tensor *tensors, int32_t n_tensors, double lr, double beta1, double beta2,
                        double eps, double max_norm, int32_t nparts, int64_t *step_dev, void *workspace_dev,
                        float *total_norm_out, void *stream) {
-  return adam_launch(tensors, n_tensors, lr, beta1, beta2, eps, max_norm, step_dev, workspace_dev, total_norm_out,
-                     nparts, false, as_stream(stream));
+  return adam_launch("rth_adam_prenormed", tensors, n_tensors, lr, beta1, beta2, eps, max_norm, step_dev, workspace_dev,
+                     total_norm_out, nparts, false, as_stream(stream));
 }
 
 }  // extern "C"
