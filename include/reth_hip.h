@@ -1001,8 +1001,10 @@ int rth_soft_update(float *const *target, const float *const *source, const int6
  * have the same order and shapes (every element written, nothing accumulated).  Built for H = 64,
  * D in 1..64, A in 2..18, any n (rth_ppo_act: up to 2^32), B >= 1; every entry point returns
  * RTH_ERR_INVALID for another shape or a row stride below D and launches nothing.
- * Every product is one fp32 fmaf and a dot product has one fixed summation order; tanh, exp and
- * log are evaluated in fp64 and rounded once.  The policy is the log-softmax of the logits z: with
+ * Every product is one fp32 fmaf and a dot product has one fixed summation order; the last layer's
+ * 64 products are summed in fp64 (increasing k, then the bias) and the logit or value rounded once,
+ * as a trained policy's logits reach the hundreds; tanh, exp and log are evaluated in fp64 and
+ * rounded once.  The policy is the log-softmax of the logits z: with
  * m = max_j z_j and s = sum_j exp(z_j - m) (fp64, increasing j), logp_j = fl32((z_j - m) - log s)
  * and p_j = fl32(exp(logp_j)).  The reference builds Categorical(probs = softmax(z)), which clamps
  * the probabilities to [1.19e-7, 1 - 1.19e-7] before taking their logarithm; this form has no

@@ -10,7 +10,8 @@
 // LDS once, as mlp.hpp does (row stride 68 floats), and walks tiles of kPpoRows rows; a forward's
 // only round trip to L2 / HBM is its input rows.  Lane j = tid % 64 owns a hidden unit, tid / 64
 // picks 2 of the tile's 8 rows.  Every product is one fmaf, a dot product has dense.hpp's ONE
-// summation order, then the bias; tanh, exp and log are evaluated in fp64 and rounded once
+// summation order, then the bias -- but the last layer's 64 products are summed in fp64 and the logit
+// (or value) rounded once; tanh, exp and log are evaluated in fp64 and rounded once
 // (ddpg.hpp's precedent).  ppo_forward_rows is the only forward and ppo_log_softmax the only
 // log-softmax, so a row's log-probability does not depend on n, on its position, on the row
 // stride or on the entry point.  The batch sums (weight and bias gradients, the mean squared
@@ -150,18 +151,23 @@ __device__ inline void ppo_forward_rows(const PpoNetSmem &w, const float (*xs)[k
   }
   __syncthreads();
   if (tid < kPpoRows * N3) {  // layer 3: one lane per (row, output)
+    // A trained policy's last weights are large: its logits reach the hundreds, and what an fp32 sum
+    // of the 64 products loses there (a spacing or two of a logit) goes whole into the
+    // log-probability and, times rho |adv|, into the loss.  The products are exact in fp64: summed
+    // there in increasing k, then the bias, the logit is rounded once.
     const int r = tid / N3, a = tid % N3;
-    float acc[8] = {};
+    double acc = 0.0;
     const float *wr = w.w3 + a * kPpoLdw;
 #pragma unroll 2
-    for (int k0 = 0; k0 < kPpoH; k0 += 8) {
+    for (int k0 = 0; k0 < kPpoH; k0 += 4) {
       const float4 wa = *reinterpret_cast<const float4 *>(wr + k0);
-      const float4 wb = *reinterpret_cast<const float4 *>(wr + k0 + 4);
       const float4 xa = *reinterpret_cast<const float4 *>(&o.h2[r][k0]);
-      const float4 xb = *reinterpret_cast<const float4 *>(&o.h2[r][k0 + 4]);
-      dense_fma8(xa, xb, wa, wb, acc);
+      acc = fma((double)xa.x, (double)wa.x, acc);
+      acc = fma((double)xa.y, (double)wa.y, acc);
+      acc = fma((double)xa.z, (double)wa.z, acc);
+      acc = fma((double)xa.w, (double)wa.w, acc);
     }
-    o.z[r][a] = radd(dense_tree8(acc), w.b3[a]);
+    o.z[r][a] = (float)(acc + (double)w.b3[a]);
   }
   __syncthreads();
 }

@@ -3,7 +3,9 @@ against rth_ppo_act on the documented draws, the dynamics against the classic-co
 the host CartPole, the rollout's finish and carry against ppo_actors.HostRollout, determinism,
 position independence / the grid-stride loop, buffer bounds and the argument checks.
 
-N in {1, 9, 64}: 9 crosses a tile of 8 rows."""
+N in {1, 9, 64}: 9 crosses a tile of 8 rows.  Segments here have cap <= 47 rows and the policies
+spread their probabilities; segments past one pass of the finish's 256 lanes (cap 399 and 4096), ragged
+counts over 600 envs and a saturated actor are in test_ppo_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -201,12 +203,12 @@ def _load_host(act, host):
     host.complete[...] = act.complete.cpu().numpy()
 
 
-def _check_finish(act, host, label):
+def _check_finish(act, host, label, gamma=GAMMA):
     """one finish on both; returns the largest |ret| difference in fp32 ulps"""
     for b in act.batch:
         b.fill_(-77)
-    (s, a, ret, lp), n_dev = act.finish(GAMMA)
-    hs, ha, hret, hlp, n = host.finish(GAMMA)
+    (s, a, ret, lp), n_dev = act.finish(gamma)
+    hs, ha, hret, hlp, n = host.finish(gamma)
     assert int(n_dev) == n, label
     assert _bits(s[:n]) == hs.tobytes() and _bits(a[:n]) == ha.tobytes() and _bits(lp[:n]) == hlp.tobytes(), label
     got = ret[:n].cpu().numpy()

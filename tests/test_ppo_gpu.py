@@ -10,7 +10,9 @@ construction, so fp32 rounding flips no clip decision; the advantage's sign need
 loss and its gradient are continuous there.  For seeds 0..39 the first is taken at which, in fp64,
 min p >= 1e-4 (the reference's clamp of the probabilities to [1.19e-7, 1 - 1.19e-7] is inactive)
 and, for B >= 64, all six (below / inside / above the clip range) x (sign of the advantage) classes
-are present.
+are present.  Saturated policies (logits in the hundreds, probabilities of 0.0f and 1.0f, where the
+clamp would be active and the kernels, which have none, compute another function than Categorical(probs))
+are in test_ppo_edges_gpu.py, against log_softmax in fp64.
 
 The error bound is the project's: |ours - fp64| <= max(1.5 |torch fp32 CPU - fp64|, 1e-6 max|fp64|)
 per tensor, the reference in both precisions being the reference's expression (Categorical,
