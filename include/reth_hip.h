@@ -1054,6 +1054,23 @@ int rth_ppo_grads_n(const float *const *actor, const float *const *value, const 
                     int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
                     float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
                     const int64_t *n_dev, void *stream);
+/* rth_ppo_grads_n with the advantage as an input: the surrogate uses adv_b = adv_dev[b] (float [B])
+ * where rth_ppo_grads forms ret_b - v_b; the value loss and its gradient still use ret_dev.  n_dev
+ * is nullable here: NULL means n = B.  Everything else -- workspace, loss_abs, loss_mean, two
+ * launches, no atomics, the checks before any launch -- is rth_ppo_grads' (one code path: with
+ * adv_b = fl32(ret_b - v_b) the results are rth_ppo_grads' bit for bit).  Rows of adv_dev at n and
+ * beyond are not read. */
+int rth_ppo_grads_adv(const float *const *actor, const float *const *value, const float *s_dev, int64_t lds,
+                      const int64_t *a_dev, const float *ret_dev, const float *adv_dev, const float *old_logprob_dev,
+                      int64_t B, int64_t D, int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef,
+                      float *const *actor_grads, float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev,
+                      void *workspace_dev, const int64_t *n_dev, void *stream);
+/* Advantage normalisation, one launch (one workgroup), in place over the first n = min(n_dev[0], B)
+ * rows (n_dev NULL: n = B): adv_b = (float) (((double) adv_b - mean) / (std + 1e-8)), mean and the
+ * population standard deviation of the fp32 advantages summed in fp64 in a fixed order (lane t of
+ * 1024 sums rows t, t + 1024, ... in increasing order, then a tree over the lanes).  n = 0 writes
+ * nothing, n = 1 writes 0.  Rows at n and beyond are neither read nor written. */
+int rth_ppo_adv_normalize(float *adv_dev, int64_t B, const int64_t *n_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-resident PPO actors on the fused actor above (csrc/ppo_actor.hpp): the on-policy rollout
@@ -1114,6 +1131,29 @@ int rth_ppo_actor_step(const rth_ppo_actor_args *args, void *stream);
  * fill[i] -= complete[i], complete[i] = 0.  Arguments are checked before anything is launched. */
 int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *batch_s_dev, int64_t *batch_a_dev,
                            float *batch_ret_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream);
+/* The end of a rollout with GAE(lambda) and a value bootstrap at the rollout's edge: the other
+ * estimator on the segments the step leaves.  `value` is the value network (HOST array of six
+ * device pointers); args->cur_obs is read (the step's other state buffers are not).  Env i
+ * contributes all of its T = fill[i] rows (0..cap): v_t = value(s_t) and v_last = value(cur_obs[i]),
+ * by the forward of rth_ppo_grads (the value that entry point computes for the row with the same
+ * weights, bit for bit), then in fp64, every operation rounded once and none contracted, backwards
+ * over t = T-1 .. 0 with run = 0:
+ *   nt    = 1 - done_t
+ *   nv    = (t == T-1) ? v_last : v_{t+1}
+ *   delta = (r_t + (gamma * nv) * nt) - v_t
+ *   run   = delta + ((gamma * lam) * nt) * run
+ *   adv_t = (float) run,   ret_t = (float) (run + (double) v_t)
+ * A done row is a terminal state whether the time limit or the dynamics ended the episode: nothing
+ * is bootstrapped through it.  The rows (s, a, ret, adv, v, logp) go to the dense batch (batch_s
+ * [., D], the others [.]; N * cap rows hold any rollout) at offset sum_{k<i} fill[k] -- env-major,
+ * then in time order -- and n_dev[0] = sum_k fill[k]; batch rows at n and beyond are left as they
+ * were.  Then fill[i] = 0, both complete slots of env i = 0 and gen[i] += 1: there is no carry.
+ * Two launches on `stream` (one workgroup per env, then the counters -- no workgroup may empty a
+ * fill another still has to sum); no atomics, no host synchronisation, graph-capturable.  gamma and
+ * lam in 0..1; arguments are checked before anything is launched. */
+int rth_ppo_gae_finish(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
+                       float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
+                       float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-resident continuous-control actors on DDPG's fused actor (csrc/ddpg_actor.hpp): one

@@ -313,6 +313,12 @@ SIGNATURES = {
     "rth_ppo_grads_n": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                                 c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                 c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rth_ppo_grads_adv": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                  c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rth_ppo_adv_normalize": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    "rth_ppo_gae_finish": (c_i32, [ctypes.POINTER(PpoActorArgs), ctypes.POINTER(c_vp), c_f64, c_f64, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp]),
     # the PPO actors, their rollout and its end (ppo_actor.hpp)
     "rth_ppo_env_reset": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),
     "rth_ppo_actor_step": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),

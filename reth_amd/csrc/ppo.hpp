@@ -17,6 +17,8 @@
 // stride or on the entry point.  The batch sums (weight and bias gradients, the mean squared
 // value error, the loss mean) are the second launch, with dense.hpp's functions in its order
 // (gradients: per chunk of 128 rows, the chunks' sums added in fp64 -- ppo_wgrad_tile): no atomics.
+// rth_ppo_grads_adv is rth_ppo_grads with the surrogate's advantage as an input (GAE:
+// ppo_actor.hpp's rth_ppo_gae_finish) and rth_ppo_adv_normalize normalises such a column in place.
 #pragma once
 #include "dense.hpp"
 
@@ -284,6 +286,7 @@ __device__ inline void ppo_dgrad_store(const PpoNetSmem &w, const PpoRows &o, fl
 __global__ __launch_bounds__(kPpoThreads) void k_ppo_tile(DenseNet ac, DenseNet va, const float *__restrict__ st,
                                                           int64_t lds, const int64_t *__restrict__ act,
                                                           const float *__restrict__ ret,
+                                                          const float *__restrict__ advp,
                                                           const float *__restrict__ old_logp, int64_t cap,
                                                           const int64_t *__restrict__ n_dev, int D, int A,
                                                           float clip_lo, float clip_hi, float vf_coef, float ent_coef,
@@ -310,7 +313,7 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_tile(DenseNet ac, DenseNet 
         const int a = a64 < 0 ? 0 : (a64 >= A ? A - 1 : (int)a64);  // (an action outside [0, A) reads in bounds)
         const float lp = s.dist.logp[tid][a];
         const float v = s.rv.z[tid][0], rt = ret[b];
-        const float adv = rsub(rt, v);
+        const float adv = advp ? advp[b] : rsub(rt, v);  // rth_ppo_grads_adv: the advantage as given
         const float rho = (float)exp((double)lp - (double)old_logp[b]);
         const float rc = rho < clip_lo ? clip_lo : (rho > clip_hi ? clip_hi : rho);
         const float s1 = rmul(rho, adv), s2 = rmul(rc, adv);
@@ -449,6 +452,41 @@ __global__ __launch_bounds__(kDenseGradThreads) void k_ppo_wgrad(DenseGrads ga, 
   if (threadIdx.x == 0 && loss_mean) loss_mean[0] = radd(rmul(sum, invB), vmse);
 }
 
+// rth_ppo_adv_normalize: adv_b = fl32((adv_b - mean) / (std + 1e-8)) over the first ppo_rows(cap, n_dev)
+// rows, in place, mean and population std of the fp32 advantages in fp64.  One workgroup; a sum is
+// lane t's serial sum over the rows b = t (mod kPpoNormThreads) in increasing b, then a tree over the
+// lanes: a fixed order.  Every row is read (twice) before the first is written.
+constexpr int kPpoNormThreads = 1024;
+
+__device__ inline double ppo_norm_sum(double acc, double *part) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // `part` is free again
+  part[tid] = acc;
+  __syncthreads();
+  for (int st = kPpoNormThreads / 2; st > 0; st >>= 1) {
+    if (tid < st) part[tid] = radd(part[tid], part[tid + st]);
+    __syncthreads();
+  }
+  return part[0];
+}
+
+__global__ __launch_bounds__(kPpoNormThreads) void k_ppo_adv_normalize(float *__restrict__ adv, int64_t cap,
+                                                                       const int64_t *__restrict__ n_dev) {
+  __shared__ double part[kPpoNormThreads];
+  const int64_t n = ppo_rows(cap, n_dev);
+  if (n == 0) return;  // (uniform)
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n; b += kPpoNormThreads) acc = radd(acc, (double)adv[b]);
+  const double mean = ppo_norm_sum(acc, part) / (double)n;
+  acc = 0.0;
+  for (int64_t b = threadIdx.x; b < n; b += kPpoNormThreads) {
+    const double c = rsub((double)adv[b], mean);
+    acc = radd(acc, rmul(c, c));
+  }
+  const double den = radd(sqrt(ppo_norm_sum(acc, part) / (double)n), 1e-8);
+  for (int64_t b = threadIdx.x; b < n; b += kPpoNormThreads) adv[b] = (float)(rsub((double)adv[b], mean) / den);
+}
+
 inline bool ppo_shape_ok(int64_t D, int64_t H, int64_t A) {
   return H == kPpoH && D >= 1 && D <= kPpoMaxD && A >= kPpoMinA && A <= kPpoMaxA;
 }
@@ -461,10 +499,11 @@ inline bool ppo_shape_ok(int64_t D, int64_t H, int64_t A) {
 // The body of rth_ppo_grads (n_dev = NULL: the batch is B rows) and rth_ppo_grads_n (B is the
 // capacity, the batch is the first min(*n_dev, B) rows): one code path.  The workspace is laid out
 // for B in both, and the chunks of kPpoChunk rows start at row 0 in both, so n rows out of a larger
-// capacity give what B = n gives, bit for bit.
+// capacity give what B = n gives, bit for bit.  rth_ppo_grads_adv is the same path with adv_dev given:
+// the surrogate's advantage is adv_dev[b] instead of ret_b - v_b, nothing else changes.
 inline int ppo_grads_run(const char *fn, const float *const *actor, const float *const *value, const float *s_dev,
-                         int64_t lds, const int64_t *a_dev, const float *ret_dev, const float *old_logprob_dev,
-                         int64_t B, const int64_t *n_dev, int64_t D, int64_t H, int64_t A, float eps_clip,
+                         int64_t lds, const int64_t *a_dev, const float *ret_dev, const float *adv_dev,
+                         const float *old_logprob_dev, int64_t B, const int64_t *n_dev, int64_t D, int64_t H, int64_t A, float eps_clip,
                          float vf_coef, float ent_coef, float *const *actor_grads, float *const *value_grads,
                          float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev, void *stream) {
   RTH_REQUIRE(ppo_shape_ok(D, H, A), "%s: unsupported shape D=%lld H=%lld A=%lld " RTH_PPO_LIMITS, fn, (long long)D,
@@ -488,7 +527,7 @@ inline int ppo_grads_run(const char *fn, const float *const *actor, const float 
   const float lo = (float)(1.0 - (double)eps_clip), hi = (float)(1.0 + (double)eps_clip);
   float *ws = static_cast<float *>(workspace_dev);
   hipLaunchKernelGGL(k_ppo_tile, dim3(dense_grid(B)), dim3(kPpoThreads), 0, as_stream(stream), ac, va, s_dev, lds,
-                     a_dev, ret_dev, old_logprob_dev, B, n_dev, (int)D, (int)A, lo, hi, vf_coef, ent_coef,
+                     a_dev, ret_dev, adv_dev, old_logprob_dev, B, n_dev, (int)D, (int)A, lo, hi, vf_coef, ent_coef,
                      (int)backward, ws);
   RTH_LAUNCHED();
   const int grad_blocks = ppo_net_blocks((int)A) + ppo_net_blocks(1);
@@ -533,8 +572,8 @@ int rth_ppo_grads(const float *const *actor, const float *const *value, const fl
                   int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef, float *const *actor_grads,
                   float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
                   void *stream) {
-  return rth::ppo_grads_run("rth_ppo_grads", actor, value, s_dev, lds, a_dev, ret_dev, old_logprob_dev, B, nullptr, D,
-                            H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
+  return rth::ppo_grads_run("rth_ppo_grads", actor, value, s_dev, lds, a_dev, ret_dev, nullptr, old_logprob_dev, B,
+                            nullptr, D, H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
                             workspace_dev, stream);
 }
 
@@ -544,9 +583,29 @@ int rth_ppo_grads_n(const float *const *actor, const float *const *value, const 
                     float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev, void *workspace_dev,
                     const int64_t *n_dev, void *stream) {
   RTH_REQUIRE(n_dev, "rth_ppo_grads_n: NULL row count");
-  return rth::ppo_grads_run("rth_ppo_grads_n", actor, value, s_dev, lds, a_dev, ret_dev, old_logprob_dev, B, n_dev, D,
-                            H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
+  return rth::ppo_grads_run("rth_ppo_grads_n", actor, value, s_dev, lds, a_dev, ret_dev, nullptr, old_logprob_dev, B,
+                            n_dev, D, H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev, loss_mean_dev,
                             workspace_dev, stream);
+}
+
+int rth_ppo_grads_adv(const float *const *actor, const float *const *value, const float *s_dev, int64_t lds,
+                      const int64_t *a_dev, const float *ret_dev, const float *adv_dev, const float *old_logprob_dev,
+                      int64_t B, int64_t D, int64_t H, int64_t A, float eps_clip, float vf_coef, float ent_coef,
+                      float *const *actor_grads, float *const *value_grads, float *loss_abs_dev, float *loss_mean_dev,
+                      void *workspace_dev, const int64_t *n_dev, void *stream) {
+  RTH_REQUIRE(adv_dev, "rth_ppo_grads_adv: NULL advantages");
+  return rth::ppo_grads_run("rth_ppo_grads_adv", actor, value, s_dev, lds, a_dev, ret_dev, adv_dev, old_logprob_dev,
+                            B, n_dev, D, H, A, eps_clip, vf_coef, ent_coef, actor_grads, value_grads, loss_abs_dev,
+                            loss_mean_dev, workspace_dev, stream);
+}
+
+int rth_ppo_adv_normalize(float *adv_dev, int64_t B, const int64_t *n_dev, void *stream) {
+  using namespace rth;
+  RTH_REQUIRE(adv_dev && B >= 1 && B <= (int64_t)1 << 40, "rth_ppo_adv_normalize: NULL advantages or bad B=%lld",
+              (long long)B);
+  hipLaunchKernelGGL(k_ppo_adv_normalize, dim3(1), dim3(kPpoNormThreads), 0, as_stream(stream), adv_dev, B, n_dev);
+  RTH_LAUNCHED();
+  return RTH_OK;
 }
 
 }  // extern "C"

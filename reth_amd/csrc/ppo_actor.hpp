@@ -2,7 +2,8 @@
 // loop (reth/examples/ppo/run.py with algorithm/util.py:27-40) kept in HBM.  Three entry points on
 // one argument block: rth_ppo_env_reset, rth_ppo_actor_step (one launch per env step of N envs) and
 // rth_ppo_rollout_finish (one launch per update: the returns of the finished episodes, the dense
-// batch, its device row count and the carry of the episodes still running).  The counterpart of
+// batch, its device row count and the carry of the episodes still running); rth_ppo_gae_finish is
+// the finish of the other estimator, GAE(lambda), on the same segments.  The counterpart of
 // env_actor.hpp for an on-policy learner; the environments, their reset draws and observation
 // maps are env_actor.hpp's (env_dynamics / env_reset_draw / env_store_obs, templated on the env):
 //   RTH_ENV_CARTPOLE D 4, A 2;  RTH_ENV_ACROBOT D 6, A 3;  RTH_ENV_MOUNTAINCAR D 2, A 3;  H = 64.
@@ -41,6 +42,25 @@
 // and n_dev[0] = sum_k complete[k]; batch rows at n and beyond are left as they were.  Then rows
 // [e, m) move to [0, m - e) with their old log-probabilities (chunks: read, barrier, write, in
 // increasing order, after the batch copy has read the segment), fill[i] = m - e, complete[i] = 0.
+//
+// The GAE finish (rth_ppo_gae_finish): the other estimator on the same segments -- GAE(lambda) with a
+// value bootstrap at the rollout's edge, every stored row of every env, no carry.  Workgroup i, with
+// T = fill[i]: the value network staged once (ppo_stage_net), rows 0..T-1 of the segment plus, as row
+// T, cur_obs[i] through ppo_forward_rows in tiles of kPpoRows -- the only forward, so v_t is what
+// k_ppo_tile computes for that row with those weights, bit for bit -- and v_last = the value of
+// cur_obs[i].  Then one lane, backwards over t = T-1 .. 0 in fp64 with run = 0, every operation
+// rounded once:
+//   nt    = 1 - done_t
+//   nv    = (t == T-1) ? v_last : v_{t+1}
+//   delta = (r_t + (gamma * nv) * nt) - v_t
+//   run   = delta + ((gamma * lam) * nt) * run
+//   adv_t = (float) run,  ret_t = (float) (run + (double) v_t)
+// A done row is a terminal state (time limit or not): the step has already put the reset draw into
+// the next observation, and nt = 0 keeps its value out.  The rows (s, a, ret, adv, v, logp) go to the
+// dense batch at offset sum_{k<i} fill[k], env-major then time, n_dev[0] = sum_k fill[k].  Nothing
+// in that launch writes fill, so every workgroup sums what the steps left; a second, small launch
+// (k_ppo_gae_clear) then sets fill[i] = 0 and both complete slots of env i = 0, and gen[i] += 1.
+// One launch would have workgroup k zero fill[k] while workgroup i > k may not have read it yet.
 #pragma once
 #include "env_actor.hpp"
 #include "ppo.hpp"
@@ -253,7 +273,85 @@ __global__ __launch_bounds__(kPpoFinThreads) void k_ppo_rollout_finish(PpoActor 
   }
 }
 
-enum { kPpoReset = 0, kPpoStep = 1, kPpoFinish = 2 };
+// The GAE finish (the header's "The GAE finish"): one workgroup per env.  r holds the rewards, then
+// the advantages; dn the done flags, then the returns; v the values of the env's rows and, at [m],
+// of cur_obs[i].  With the staged value network that is 98 KB of a CU's 160 KB of LDS at any cap.
+struct PpoGaeSmem {
+  PpoNetSmem value;
+  PpoRows rv;
+  float x[kPpoRows][kPpoMaxD];
+  float r[kPpoMaxCap], dn[kPpoMaxCap], v[kPpoMaxCap + 4];
+  int64_t red[kPpoThreads];
+};
+
+__global__ __launch_bounds__(kPpoThreads) void k_ppo_gae_finish(PpoActor a, DenseNet va, int D, int LD, double gamma,
+                                                                double lam, float *__restrict__ bs,
+                                                                int64_t *__restrict__ ba, float *__restrict__ bret,
+                                                                float *__restrict__ badv, float *__restrict__ bv,
+                                                                float *__restrict__ blogp,
+                                                                int64_t *__restrict__ n_dev) {
+  __shared__ __align__(16) PpoGaeSmem s;
+  const int tid = threadIdx.x, cap = a.cap;
+  const int64_t i = blockIdx.x, N = a.N, base = i * cap;
+  const int m = ppo_clampi(a.fill[i], 0, cap);  // no launch of this kernel writes fill: k_ppo_gae_clear does
+  int64_t acc = 0;  // the batch offset: an integer sum, so its order is free
+  for (int64_t k = tid; k < i; k += kPpoThreads) acc += ppo_clampi(a.fill[k], 0, cap);
+  s.red[tid] = acc;
+  for (int t = tid; t < m; t += kPpoThreads) s.r[t] = a.seg_r[base + t], s.dn[t] = a.seg_done[base + t];
+  if (m > 0) ppo_stage_net(va, D, 1, s.value);  // (uniform)
+  __syncthreads();
+  for (int st = kPpoThreads / 2; st > 0; st >>= 1) {
+    if (tid < st) s.red[tid] += s.red[tid + st];
+    __syncthreads();
+  }
+  const int64_t off = s.red[0];
+  if (i == N - 1 && tid == 0) n_dev[0] = off + m;
+  if (m == 0) return;  // (uniform)
+  // the values of rows 0..m-1 and, as row m, of the observation the env acts on next
+  for (int r0 = 0; r0 <= m; r0 += kPpoRows) {
+    __syncthreads();
+    for (int e = tid; e < kPpoRows * kPpoMaxD; e += kPpoThreads) {
+      const int r = e / kPpoMaxD, k = e % kPpoMaxD, q = r0 + r;
+      float x = 0.0f;
+      if (k < D && q <= m) x = q < m ? a.seg_s[(base + q) * D + k] : a.cur_obs[i * LD + k];
+      s.x[r][k] = x;
+    }
+    ppo_forward_rows(s.value, s.x, D, 1, s.rv);
+    if (tid < kPpoRows && r0 + tid <= m) s.v[r0 + tid] = s.rv.z[tid][0];
+  }
+  __syncthreads();
+  if (tid == 0) {  // the scan: serial, fp64, every operation rounded once
+    const double gl = rmul(gamma, lam);
+    double run = 0.0;
+    for (int t = m - 1; t >= 0; --t) {
+      const double nt = rsub(1.0, (double)s.dn[t]), vt = (double)s.v[t];
+      const double delta = rsub(radd((double)s.r[t], rmul(rmul(gamma, (double)s.v[t + 1]), nt)), vt);
+      run = radd(delta, rmul(rmul(gl, nt), run));
+      s.r[t] = (float)run;
+      s.dn[t] = (float)radd(run, vt);
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < m; t += kPpoThreads) {
+    ba[off + t] = a.seg_a[base + t];
+    blogp[off + t] = a.seg_logp[base + t];
+    badv[off + t] = s.r[t];
+    bret[off + t] = s.dn[t];
+    bv[off + t] = s.v[t];
+  }
+  for (int e = tid; e < m * D; e += kPpoThreads) bs[off * D + e] = a.seg_s[base * D + e];
+}
+
+// ... and the segments emptied, after every workgroup above has summed the fills
+__global__ __launch_bounds__(256) void k_ppo_gae_clear(PpoActor a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.N) return;
+  a.fill[i] = 0;
+  a.complete[i] = 0, a.complete[a.N + i] = 0;
+  a.gen[i] += 1;
+}
+
+enum { kPpoReset = 0, kPpoStep = 1, kPpoFinish = 2, kPpoGae = 3 };
 
 // the argument checks of the three entry points
 inline const char *ppo_actor_check(const rth_ppo_actor_args *x, int what, PpoActor *out) {
@@ -268,7 +366,9 @@ inline const char *ppo_actor_check(const rth_ppo_actor_args *x, int what, PpoAct
   if (x->max_episode_steps < 1) return "bad max_episode_steps (>= 1)";
   if (!x->fill || !x->complete || !x->gen || !x->dropped) return "NULL rollout counter";
   PpoActor a{};
-  if (what != kPpoFinish) {
+  if (what == kPpoGae) {
+    if (!x->cur_obs) return "NULL cur_obs";
+  } else if (what != kPpoFinish) {
     if (!x->state || !x->ep_steps || !x->t_dev || !x->stats || !x->ret_stats || !x->cur_obs)
       return "NULL state buffer";
     if (reinterpret_cast<uintptr_t>(x->cur_obs) & 15) return "cur_obs must be 16-byte aligned";
@@ -331,6 +431,29 @@ int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *
   hipLaunchKernelGGL(k_ppo_rollout_finish, dim3((unsigned)a.N), dim3(kPpoFinThreads), (size_t)a.cap * 8,
                      as_stream(stream), a, (int)args->D, gamma, batch_s_dev, batch_a_dev, batch_ret_dev,
                      batch_logprob_dev, n_dev);
+  RTH_LAUNCHED();
+  return RTH_OK;
+}
+
+int rth_ppo_gae_finish(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
+                       float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
+                       float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream) {
+  using namespace rth;
+  PpoActor a;
+  const char *bad = ppo_actor_check(args, kPpoGae, &a);
+  RTH_REQUIRE(!bad, "rth_ppo_gae_finish: %s", bad);
+  DenseNet va;
+  RTH_REQUIRE(dense_net(value, &va), "rth_ppo_gae_finish: NULL value network parameter");
+  RTH_REQUIRE(batch_s_dev && batch_a_dev && batch_ret_dev && batch_adv_dev && batch_v_dev && batch_logprob_dev && n_dev,
+              "rth_ppo_gae_finish: NULL batch buffer");
+  RTH_REQUIRE(gamma >= 0.0 && gamma <= 1.0 && lam >= 0.0 && lam <= 1.0,
+              "rth_ppo_gae_finish: bad gamma %g or lambda %g (0..1)", gamma, lam);
+  const int D = (int)args->D;
+  hipLaunchKernelGGL(k_ppo_gae_finish, dim3((unsigned)a.N), dim3(kPpoThreads), 0, as_stream(stream), a, va, D,
+                     env_ld(D), gamma, lam, batch_s_dev, batch_a_dev, batch_ret_dev, batch_adv_dev, batch_v_dev,
+                     batch_logprob_dev, n_dev);
+  RTH_LAUNCHED();
+  hipLaunchKernelGGL(k_ppo_gae_clear, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, as_stream(stream), a);
   RTH_LAUNCHED();
   return RTH_OK;
 }

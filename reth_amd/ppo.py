@@ -228,23 +228,27 @@ class PPOSolver(Algorithm):
         return x if x.stride(1) == 1 and x.stride(0) >= cols else x.contiguous()
 
     def _hip_update(self, batch, n_rows=None):
-        states, actions, returns, logprobs = batch
+        states, actions, returns, logprobs = batch[:4]
         D, H, A = self.dims
         s = self._matrix(states, D)
         a = self._tensor(actions, torch.long).reshape(-1).contiguous()
         ret = self._tensor(returns, torch.float32).reshape(-1).contiguous()
         old = self._tensor(logprobs, torch.float32).reshape(-1).contiguous()
         B = s.shape[0]
-        if a.numel() != B or ret.numel() != B or old.numel() != B:
+        adv = self._tensor(batch[4], torch.float32).reshape(-1).contiguous() if len(batch) == 5 else None
+        if a.numel() != B or ret.numel() != B or old.numel() != B or (adv is not None and adv.numel() != B):
             raise ValueError("batch columns disagree in length")
         if n_rows is not None and not (torch.is_tensor(n_rows) and n_rows.device == self.device
                                        and n_rows.dtype == torch.int64 and n_rows.numel() == 1):
             raise ValueError("n_rows: an int64 tensor [1] on the solver's device")
         ws, loss_abs, loss_mean = self._buffers(B)
         fn, count = ("rth_ppo_grads", ()) if n_rows is None else ("rth_ppo_grads_n", (ptr(n_rows),))
+        given = ()
+        if adv is not None:  # the advantage as given, with or without a device row count
+            fn, given, count = "rth_ppo_grads_adv", (ptr(adv),), (ptr(n_rows),)
         for _ in range(self.k_epochs):
             p = self._arrays()
-            call(fn, p["actor"], p["value"], ptr(s), s.stride(0), ptr(a), ptr(ret), ptr(old), B, D, H, A,
+            call(fn, p["actor"], p["value"], ptr(s), s.stride(0), ptr(a), ptr(ret), *given, ptr(old), B, D, H, A,
                  float(self.eps_clip), VF_COEF, ENT_COEF, p["actor_grads"], p["value_grads"], ptr(loss_abs),
                  ptr(loss_mean), ptr(ws), *count, stream_ptr())
             self.actor_optimizer.step()
@@ -275,7 +279,8 @@ class PPOSolver(Algorithm):
         return dist.log_prob(action), torch.squeeze(self.value_network(state)), dist.entropy()
 
     def _torch_update(self, batch):
-        states, actions, rewards, logprobs = batch
+        states, actions, rewards, logprobs = batch[:4]
+        given = self._tensor(batch[4], torch.float32) if len(batch) == 5 else None
         actions = self._tensor(actions, torch.long)
         states = self._tensor(states, torch.float32)
         rewards = self._tensor(rewards, torch.float32)
@@ -283,7 +288,7 @@ class PPOSolver(Algorithm):
         for _ in range(self.k_epochs):
             new_logprobs, state_values, dist_entropy = self._evaluate_policy(states, actions)
             ratios = torch.exp(new_logprobs - logprobs.detach())
-            advantages = rewards - state_values.detach()
+            advantages = rewards - state_values.detach() if given is None else given
             surr1 = ratios * advantages
             surr2 = torch.clamp(ratios, 1 - self.eps_clip, 1 + self.eps_clip) * advantages
             loss = -torch.min(surr1, surr2) + VF_COEF * F.mse_loss(state_values, rewards) - ENT_COEF * dist_entropy
@@ -302,7 +307,11 @@ class PPOSolver(Algorithm):
         (weights is accepted and ignored, as in the reference).  n_rows (a device int64 [1]): the
         batch is the first min(n_rows, B) rows of the columns, counted on the device
         (rth_ppo_grads_n; buffers are kept per capacity B, and |loss| beyond the count is stale).
-        The torch path reads n_rows on the host and slices: the yardstick only."""
+        The torch path reads n_rows on the host and slices: the yardstick only.  A fifth column,
+        the advantages, is taken as given where the reference forms returns - values (GAE:
+        ppo_actors.finish_gae); the value loss still uses the returns (rth_ppo_grads_adv)."""
+        if len(batch) not in (4, 5):
+            raise ValueError("batch: (states, actions, returns, old log-probabilities[, advantages])")
         if self.impl_active == "hip":
             return self._hip_update(batch, n_rows)
         if n_rows is not None:

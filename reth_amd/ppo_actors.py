@@ -23,7 +23,13 @@ A segment holds cap = horizon + max_episode_steps - 1 rows: a rollout of `horizo
 carried episode, which has at most max_episode_steps - 1 rows.  So nothing is ever dropped
 (`dropped` stays 0) as long as finish() follows every `horizon` steps.
 
-HostRollout restates the store, the finish and the carry in numpy with the kernel's arithmetic in
+finish_gae(value, gamma, lam) is the other estimator on the same segments: GAE(lambda) with the
+value network's bootstrap at the rollout's edge (rth_ppo_gae_finish; gae() below is its scan).
+Every stored row of every env enters the batch, with its advantage and its value as further
+columns, and the segments are empty afterwards: there is no carry, so cap = horizon rows hold a
+rollout (the keyword cap) and any horizon >= 1 runs.
+
+HostRollout restates the store, the finishes and the carry in numpy with the kernel's arithmetic in
 its order: the oracle of the GPU tests, testable without a GPU.
 """
 import numpy as np
@@ -47,16 +53,22 @@ class VecPpoActors(VecEnvActors):
     ppo.ActorNetwork) at the env's (obs_dim, 64, num_actions).  horizon: the env steps between two
     finish() calls, which sizes the segments (module docstring).  cur_obs rows are obs_dim rounded
     up to 4 floats (the pad stays 0).  Episode statistics in int64 (episode_stats) and fp64 returns
-    (return_stats).  max_episode_steps defaults to the env's TimeLimit."""
+    (return_stats).  max_episode_steps defaults to the env's TimeLimit.  cap: the rows per env's
+    segment, 1..4096; None is finish()'s rule, horizon + max_episode_steps - 1."""
     _envs = ENVS
 
-    def __init__(self, env, n_actors, horizon, seed=0, max_episode_steps=None, device=None):
+    def __init__(self, env, n_actors, horizon, seed=0, max_episode_steps=None, device=None, cap=None):
         self.horizon = int(horizon)
         super().__init__(env, n_actors, seed, max_episode_steps, device, horizon=self.horizon)
         self.num_actions = ENVS[env][2]
-        self.cap = self.horizon + self.max_episode_steps - 1
-        if self.cap > MAX_CAP:
-            raise ValueError(f"horizon + max_episode_steps - 1 = {self.cap} rows per env: at most {MAX_CAP}")
+        if cap is None:
+            self.cap = self.horizon + self.max_episode_steps - 1
+            if self.cap > MAX_CAP:
+                raise ValueError(f"horizon + max_episode_steps - 1 = {self.cap} rows per env: at most {MAX_CAP}")
+        else:  # finish_gae() has no carry: cap = horizon rows hold a rollout
+            self.cap = int(cap)
+            if not 1 <= self.cap <= MAX_CAP:
+                raise ValueError(f"cap = {self.cap} rows per env: 1..{MAX_CAP}")
         N, D, cap, z = self.N, self.obs_dim, self.cap, self._alloc
         self.cur_obs = z((N, self.ld), torch.float32)
         self.last_action, self.last_logprob = z((N,), torch.int64), z((N,), torch.float32)
@@ -69,7 +81,10 @@ class VecPpoActors(VecEnvActors):
         self.batch = [z((N * cap, D), torch.float32), z((N * cap,), torch.int64), z((N * cap,), torch.float32),
                       z((N * cap,), torch.float32)]
         self.n_dev = z((1,), torch.int64)
-        self.finishes = 0  # finish() calls: one launch each
+        self.finishes = 0  # finish() / finish_gae() calls
+        self.normalizes = 0  # rth_ppo_adv_normalize calls
+        self.batch_adv = self.batch_v = None  # finish_gae()'s further columns, made by its first call
+        self._value_key = self._value_arr = None
         self.reset()
 
     # ------------------------------------------------------------------ ABI arguments
@@ -158,6 +173,62 @@ class VecPpoActors(VecEnvActors):
         self.finishes += 1
         return self.batch, self.n_dev
 
+    def _value_params(self, solver_or_value):
+        """the six parameter pointers of the value network as the ABI's array (as _params)"""
+        value = getattr(solver_or_value, "value_network", solver_or_value)
+        ps = _params6(value)
+        key = tuple(p.data_ptr() for p in ps)
+        if key != self._value_key:
+            dims = tuple(int(v) for v in _dims(value))
+            ok = all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps)
+            if not ok or dims != (self.obs_dim, H, H, 1):
+                raise ValueError(f"the {self.name} GAE finish runs ppo.ValueNetwork(({self.obs_dim},), 1, {H}) in "
+                                 f"contiguous float32 on the GPU, got dims (D, H1, H2, outputs) = {dims}")
+            self._value_arr = (_lib.c_vp * 6)(*key)
+            self._value_key = key
+        return self._value_arr
+
+    @torch.no_grad()
+    def finish_gae(self, solver_or_value, gamma, lam, normalize=False):
+        """the end of a rollout with GAE(lambda), one ABI call: ([s, a, ret, logp, adv], n_dev) with
+        every stored row of every env (env-major, then time), the values of a PPOSolver's value
+        network (or a ppo.ValueNetwork) and its value of cur_obs as the bootstrap (gae() below is
+        the arithmetic).  The segments are empty afterwards: no carry.  batch_v holds the rows'
+        values.  normalize: one more call, rth_ppo_adv_normalize over the n rows.  Persistent
+        tensors, as finish()'s; rows at n and beyond are stale."""
+        if self.batch_adv is None:
+            self.batch_adv, self.batch_v = (self._alloc((self.N * self.cap,), torch.float32) for _ in range(2))
+        args = self._args()
+        s, a, ret, logp = self.batch
+        call("rth_ppo_gae_finish", _lib.ctypes.byref(args), self._value_params(solver_or_value), float(gamma),
+             float(lam), ptr(s), ptr(a), ptr(ret), ptr(self.batch_adv), ptr(self.batch_v), ptr(logp), ptr(self.n_dev),
+             stream_ptr())
+        self.finishes += 1
+        if normalize:
+            call("rth_ppo_adv_normalize", ptr(self.batch_adv), self.N * self.cap, ptr(self.n_dev), stream_ptr())
+            self.normalizes += 1
+        return [s, a, ret, logp, self.batch_adv], self.n_dev
+
+
+def gae(r, done, v, v_last, gamma, lam, dtype=np.float32):
+    """the kernel's GAE(lambda) of ONE env's rows (csrc/ppo_actor.hpp): (adv, ret) float32 [T] from
+    float32 rewards, done flags and values and the value v_last of the state behind the last row;
+    fp64, every operation rounded once, in the kernel's order (dtype=np.float64: before the final
+    rounding)"""
+    r, done, v = (np.asarray(x, np.float32).astype(np.float64) for x in (r, done, v))
+    T = len(r)
+    adv, ret = np.zeros(T, dtype), np.zeros(T, dtype)
+    g = np.float64(gamma)
+    gl = g * np.float64(lam)
+    nv, run = np.float64(np.float32(v_last)), np.float64(0.0)
+    for t in range(T - 1, -1, -1):
+        nt = np.float64(1.0) - done[t]
+        delta = (r[t] + (g * nv) * nt) - v[t]
+        run = delta + (gl * nt) * run
+        adv[t], ret[t] = run, run + v[t]  # rounded once by the store
+        nv = v[t]
+    return adv, ret
+
 
 def episode_returns(r, done, gamma):
     """the kernel's returns of ONE episode (float32 [L] from float32 rewards and done flags):
@@ -227,3 +298,18 @@ class HostRollout:
             self.fill[i], self.complete[i] = m - e, 0
         s, a, ret, logp = (np.concatenate(o) for o in out)
         return s, a, ret, logp, len(a)
+
+    def finish_gae(self, v, v_last, gamma, lam):
+        """(s [n, D], a [n], ret [n], logp [n], adv [n], n): every stored row of every env,
+        env-major, then in time order, with gae() on the rows' values v [N, cap] and the bootstrap
+        values v_last [N]; the segments are empty afterwards"""
+        v, v_last = np.asarray(v, np.float32).reshape(self.N, self.cap), np.asarray(v_last, np.float32).reshape(self.N)
+        out = [[], [], [], [], []]
+        for i in range(self.N):
+            m = int(self.fill[i])
+            adv, ret = gae(self.seg_r[i, :m], self.seg_done[i, :m], v[i, :m], v_last[i], gamma, lam)
+            for o, col in zip(out, (self.seg_s[i, :m], self.seg_a[i, :m], ret, self.seg_logp[i, :m], adv)):
+                o.append(col.copy())
+        self.fill[:], self.complete[:] = 0, 0
+        s, a, ret, logp, adv = (np.concatenate(o) for o in out)
+        return s, a, ret, logp, adv, len(a)

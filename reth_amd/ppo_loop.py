@@ -26,6 +26,14 @@ horizon >= max_episode_steps is required: then every env finishes at least one e
 iteration and a batch has at least N rows (the reference's loop has no defined behaviour for an
 empty batch either).
 
+PpoLoopConfig.gae_lambda switches the estimator: GAE(lambda) with a value bootstrap at the rollout's
+edge (ppo_actors.finish_gae, csrc/ppo_actor.hpp) instead of whole episodes' Monte-Carlo returns.
+Then any horizon >= 1 runs, a segment is `horizon` rows without a carry, every stored row reaches
+the learner at once (a batch is N * horizon rows), and step 2 / 3 become finish_gae and
+update_device on the 5-column batch (rth_ppo_grads_adv): horizon + 1 (+ 1 with normalize_adv, the
+advantages' normalisation) + 3 k_epochs ABI calls.  Many envs on short rollouts -- 64 x 32 -- is
+what that is for.  None leaves everything above as it is.
+
 The loop needs PPO's fused kernels (PPOSolver.impl_active == "hip"): without them it refuses to
 construct -- there is no torch fallback here.  It is not a device_loop.OneStreamLoop, which is
 replay-shaped (rows flow into a replay, a batch is sampled out of it).
@@ -51,6 +59,8 @@ class PpoLoopConfig:
     learning_rate: float = 0.01
     max_episode_steps: Optional[int] = None  # None: the env's TimeLimit
     seed: int = 0
+    gae_lambda: Optional[float] = None  # None: the reference's estimator; else GAE(lambda), any horizon >= 1
+    normalize_adv: bool = False        # GAE only: the batch's advantages to mean 0, std 1
 
 
 class PpoLoop:
@@ -62,7 +72,14 @@ class PpoLoop:
         self.device = torch.device(device if device is not None else "cuda")
         _, obs_dim, num_actions, limit = ENVS[cfg.env]
         self.max_episode_steps = int(limit if cfg.max_episode_steps is None else cfg.max_episode_steps)
-        if cfg.horizon < self.max_episode_steps:
+        self.gae = cfg.gae_lambda is not None
+        if cfg.normalize_adv and not self.gae:
+            raise ValueError("PpoLoopConfig.normalize_adv normalises GAE's advantages: set gae_lambda")
+        if self.gae and not 0.0 <= cfg.gae_lambda <= 1.0:
+            raise ValueError(f"PpoLoopConfig.gae_lambda {cfg.gae_lambda}: None or 0..1")
+        if self.gae and cfg.horizon < 1:
+            raise ValueError(f"PpoLoopConfig.horizon {cfg.horizon}: at least 1")
+        if not self.gae and cfg.horizon < self.max_episode_steps:
             raise ValueError(f"PpoLoopConfig.horizon {cfg.horizon} < max_episode_steps {self.max_episode_steps}: an "
                              "iteration must let every env finish an episode, or a batch could be empty")
         torch.manual_seed(cfg.seed)
@@ -72,7 +89,8 @@ class PpoLoop:
             raise RuntimeError("PpoLoop runs on PPO's fused kernels: the solver's active path is "
                                f"{self.solver.impl_active!r} (impl={impl!r}); there is no torch fallback")
         self.actors = VecPpoActors(cfg.env, cfg.n_actors, cfg.horizon, seed=cfg.seed,
-                                   max_episode_steps=self.max_episode_steps, device=self.device)
+                                   max_episode_steps=self.max_episode_steps, device=self.device,
+                                   cap=cfg.horizon if self.gae else None)  # GAE: no carry
         self.iterations = self.env_steps = self.updates = 0
         self.last_loss_abs = None  # the last update's |loss| [N * cap]: rows beyond the batch are stale
         self._graph = None
@@ -83,7 +101,10 @@ class PpoLoop:
         act = self.actors
         for _ in range(self.cfg.horizon):
             act.step(self.solver)
-        batch, n_dev = act.finish(self.cfg.gamma)
+        if self.gae:
+            batch, n_dev = act.finish_gae(self.solver, self.cfg.gamma, self.cfg.gae_lambda, self.cfg.normalize_adv)
+        else:
+            batch, n_dev = act.finish(self.cfg.gamma)
         return self.solver.update_device(batch, n_rows=n_dev)
 
     def _mirrors(self):
@@ -92,6 +113,7 @@ class PpoLoop:
         iteration() advances them after every replay"""
         act, T = self.actors, self.cfg.horizon
         return [(act, "pushes", T), (act, "launches", T), (act, "finishes", 1),
+                (act, "normalizes", int(self.gae and self.cfg.normalize_adv)),
                 (self.solver, "hip_launches", 3 * self.cfg.k_epochs)]
 
     def iteration(self):
@@ -144,11 +166,13 @@ class PpoLoop:
     @torch.no_grad()
     def rollout_length(self, seed=12345):
         """the same measure for the current actor on a separate set of n_actors envs stepped
-        `horizon` times (every env finishes an episode: horizon >= max_episode_steps), which leaves
-        the loop's own envs and rollout as they are.  Before the first update: the untrained
-        actor's figure.  One host read."""
-        ev = VecPpoActors(self.cfg.env, self.cfg.n_actors, self.cfg.horizon, seed=seed,
-                          max_episode_steps=self.max_episode_steps, device=self.device)
-        for _ in range(self.cfg.horizon):
+        max(horizon, max_episode_steps) times (every env finishes an episode; without GAE that is
+        `horizon`), which leaves the loop's own envs and rollout as they are.  Before the first
+        update: the untrained actor's figure.  One host read."""
+        steps = max(self.cfg.horizon, self.max_episode_steps)
+        # (its rows are never finished: with GAE a segment of one row, the rest counted in `dropped`)
+        ev = VecPpoActors(self.cfg.env, self.cfg.n_actors, steps, seed=seed,
+                          max_episode_steps=self.max_episode_steps, device=self.device, cap=1 if self.gae else None)
+        for _ in range(steps):
             ev.step(self.solver)
         return float(ev.episode_stats()[2].double().mean().item())
