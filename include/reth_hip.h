@@ -1071,6 +1071,32 @@ int rth_ppo_grads_adv(const float *const *actor, const float *const *value, cons
  * 1024 sums rows t, t + 1024, ... in increasing order, then a tree over the lanes).  n = 0 writes
  * nothing, n = 1 writes 0.  Rows at n and beyond are neither read nor written. */
 int rth_ppo_adv_normalize(float *adv_dev, int64_t B, const int64_t *n_dev, void *stream);
+/* Shuffled minibatches (csrc/ppo_shuffle.hpp): a counter-based random permutation of the batch's
+ * first n = min(max(n_dev[0], 0), B) rows (n_dev NULL: n = B), drawn on the device, and the batch
+ * laid out as K dense minibatches.  With M = ceil(n / K) (0 when n = 0) and the pitch Mcap =
+ * ceil(B / K):
+ *   key_i   = keys_in[i] (uint64 [B]) where given, else c[0] | (uint64) c[1] << 32 of Philox4x32-10 on
+ *             the block {lane = i, (uint32) c, (uint32) (c >> 32), stream word 14}, c = counter_dev[0],
+ *             key (seed lo, seed hi)
+ *   perm    = the STABLE argsort of key[0..n): perm_dev[q] = i where q = #{j < n : key_j < key_i, or
+ *             key_j == key_i and j < i}; perm_dev[n..B) is not written
+ *   gather  position q < n is minibatch m = q / M, place j = q % M: row perm[q] of every column goes,
+ *           bits unchanged, to row m * Mcap + j of the mb_* columns (mb_s_dev: [K * Mcap, D] dense; the
+ *           source has row stride lds >= D); rows that are no position's destination are neither read
+ *           nor written
+ *   mb_n_dev[m] = clamp(n - m * M, 0, M), m < K
+ * and afterwards counter_dev[0] += 1, with keys_in or without (in the second launch; the first one
+ * reads it).  adv_dev and mb_adv_dev are both given or both NULL.  Minibatch m is then the batch
+ * (mb_s_dev + m * Mcap * D, ...) of capacity Mcap and device row count mb_n_dev + m for
+ * rth_ppo_grads_n / rth_ppo_grads_adv.  B in 1..65,536, D in 1..64, K in 1..64 and K <= B; the
+ * workspace holds the keys (rth_ppo_shuffle_workspace(B) bytes).  Two launches, no atomics, no host
+ * synchronisation or allocation; the checks come before any launch (RTH_ERR_INVALID). */
+int64_t rth_ppo_shuffle_workspace(int64_t B); /* bytes; < 0: error */
+int rth_ppo_shuffle(const float *s_dev, int64_t lds, const int64_t *a_dev, const float *ret_dev, const float *adv_dev,
+                    const float *old_logprob_dev, int64_t B, const int64_t *n_dev, int64_t D, int64_t K, uint64_t seed,
+                    int64_t *counter_dev, const uint64_t *keys_in, float *mb_s_dev, int64_t *mb_a_dev,
+                    float *mb_ret_dev, float *mb_adv_dev, float *mb_logprob_dev, int64_t *mb_n_dev, int32_t *perm_dev,
+                    void *workspace_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-resident PPO actors on the fused actor above (csrc/ppo_actor.hpp): the on-policy rollout

@@ -317,6 +317,9 @@ SIGNATURES = {
                                   c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, ctypes.POINTER(c_vp),
                                   ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rth_ppo_adv_normalize": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    "rth_ppo_shuffle_workspace": (c_i64, [c_i64]),
+    "rth_ppo_shuffle": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rth_ppo_gae_finish": (c_i32, [ctypes.POINTER(PpoActorArgs), ctypes.POINTER(c_vp), c_f64, c_f64, c_vp, c_vp, c_vp,
                                    c_vp, c_vp, c_vp, c_vp, c_vp]),
     # the PPO actors, their rollout and its end (ppo_actor.hpp)

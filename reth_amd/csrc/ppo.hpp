@@ -19,6 +19,8 @@
 // (gradients: per chunk of 128 rows, the chunks' sums added in fp64 -- ppo_wgrad_tile): no atomics.
 // rth_ppo_grads_adv is rth_ppo_grads with the surrogate's advantage as an input (GAE:
 // ppo_actor.hpp's rth_ppo_gae_finish) and rth_ppo_adv_normalize normalises such a column in place.
+// ppo_shuffle.hpp's rth_ppo_shuffle lays a batch out as K shuffled minibatches, each of which goes
+// through rth_ppo_grads_n / rth_ppo_grads_adv as a batch of its own.
 #pragma once
 #include "dense.hpp"
 

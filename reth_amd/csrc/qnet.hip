@@ -1074,6 +1074,7 @@ int rth_linear_relu_rows_upto(const float *x, int64_t ldx, int64_t r0, int64_t n
 #include "mlp.hpp"  // the MLP Q-network: rth_mlp_q, rth_mlp_dqn_grads
 #include "ddpg.hpp"  // DDPG's actor and critic: rth_ddpg_act, rth_ddpg_critic_grads, rth_ddpg_actor_grads, rth_soft_update
 #include "ppo.hpp"  // PPO's actor and value network: rth_ppo_act, rth_ppo_grads, rth_ppo_grads_n, rth_ppo_grads_adv, rth_ppo_adv_normalize
+#include "ppo_shuffle.hpp"  // its shuffled minibatches: rth_ppo_shuffle, rth_ppo_shuffle_workspace
 #include "env_actor.hpp"  // the classic-control actors on the MLP: one step kernel; rth_env_reset, rth_env_actor_step
 #include "ppo_actor.hpp"  // the PPO actors on them: rth_ppo_env_reset, rth_ppo_actor_step, rth_ppo_rollout_finish, rth_ppo_gae_finish
 #include "mlp_actor.hpp"  // its CartPole adapters: rth_cartpole_reset, rth_mlp_actor_step

@@ -15,6 +15,9 @@ launch, which draws the action by inverse CDF from a counter-based Philox unifor
 solver's seed, its call counter, the row).  impl=None takes "hip" where it applies (a GPU, fp32,
 a shape rth_ppo_supported builds) and "torch" elsewhere; asked for explicitly, "hip" raises
 instead.  solver.impl_active names the path that runs and solver.hip_launches counts its ABI calls.
+n_minibatches = K > 1 turns every epoch into a shuffled pass of K optimiser steps: rth_ppo_shuffle
+(csrc/ppo_shuffle.hpp) draws the order on the device and the same gradient kernels take each slice;
+shuffle_keys / minibatch_perm restate the order in numpy.
 
 The kernels take the log-softmax of the logits; the reference's Categorical(probs=softmax(z))
 clamps the probabilities to [1.19e-7, 1 - 1.19e-7] first.  The two agree wherever no probability
@@ -128,15 +131,71 @@ def calculate_discount_rewards(r, gamma=0.99):
     return _normalise(discounted_r)
 
 
+# ---------------------------------------------------------------------- shuffled minibatches
+# The host restatement of rth_ppo_shuffle's permutation (csrc/ppo_shuffle.hpp), in numpy alone.
+STREAM_PPO_SHUFFLE = 14  # the shuffle keys' Philox stream word
+MAX_MINIBATCHES, MAX_SHUFFLE_ROWS = 64, 65536  # rth_ppo_shuffle's limits on K and B
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (csrc/common.hpp) on arrays of counter words, broadcast against each other;
+    the four output words as uint32 arrays.  The 32-bit words live in uint64 lanes, where a
+    32 x 32 product is exact."""
+    u = lambda v: np.asarray(v, dtype=np.uint64) & _U32
+    c0, c1, c2, c3 = np.broadcast_arrays(u(c0), u(c1), u(c2), u(c3))
+    k0, k1 = u(k0), u(k1)
+    for rnd in range(10):
+        if rnd:
+            k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _U32, (k1 + np.uint64(0xBB67AE85)) & _U32
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _U32
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def shuffle_keys(seed, counter, n):
+    """the n sort keys of shuffle number `counter` under `seed`: uint64 [n], all 64 bits of
+    c[0] | c[1] << 32 of the block {lane i, counter lo, counter hi, 14} under the key (seed lo, seed hi)"""
+    seed, counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    lanes = np.arange(int(n), dtype=np.uint64)
+    c = philox4x32(lanes, counter & 0xFFFFFFFF, counter >> 32, STREAM_PPO_SHUFFLE, seed & 0xFFFFFFFF, seed >> 32)
+    return c[0].astype(np.uint64) | (c[1].astype(np.uint64) << np.uint64(32))
+
+
+def minibatch_perm(seed, counter, n, K, keys=None):
+    """(perm int64 [n], sizes int64 [K]) of one shuffled pass over n rows in K minibatches: perm is
+    the stable argsort of the keys (shuffle_keys, or `keys`' first n), minibatch m is the rows
+    perm[m * M : m * M + sizes[m]] with M = ceil(n / K) and sizes[m] = clamp(n - m * M, 0, M)"""
+    n, K = int(n), int(K)
+    keys = shuffle_keys(seed, counter, n) if keys is None else np.asarray(keys, dtype=np.uint64)[:n]
+    perm = np.argsort(keys, kind="stable").astype(np.int64)
+    M = -(-n // K)
+    sizes = np.clip(n - np.arange(K, dtype=np.int64) * M, 0, M)
+    return perm, sizes
+
+
 class PPOSolver(Algorithm):
-    """ppo_solver.py:15-125 with its constructor arguments, plus impl (module docstring).
-    update_device's |loss| on the HIP path is a persistent buffer per batch size, overwritten by
-    the next call of that size (a captured update replays into it)."""
+    """ppo_solver.py:15-125 with its constructor arguments, plus impl (module docstring) and
+    n_minibatches.  update_device's |loss| on the HIP path is a persistent buffer per batch size,
+    overwritten by the next call of that size (a captured update replays into it).
+
+    n_minibatches = K > 1: each of the k_epochs passes draws a new random order of the batch's rows
+    (minibatch_perm of the solver's seed and shuffle_calls, which counts the passes) and takes one
+    optimiser step on each of K minibatches of M = ceil(n / K) rows, in increasing order; the last may
+    be shorter.  On the HIP path a pass is one rth_ppo_shuffle, which draws the order on the device and
+    lays the batch out as K slices of pitch Mcap = ceil(B / K), then per slice the gradient call
+    (rth_ppo_grads_adv / rth_ppo_grads_n with the slice's device row count) and the two Adam steps:
+    k_epochs (1 + 3 K) ABI calls.  A slice without rows (n < K (K - 1) + 1 can leave some) is an Adam
+    step on zero gradients there; the torch path refuses it.  K = 1 is the full-batch epoch, without
+    a shuffle."""
 
     def __init__(self, observation_space, action_space, models=None, k_epochs=4, eps_clip=0.2, learning_rate=0.01,
-                 hidden_size=64, device=None, impl=None):
+                 hidden_size=64, device=None, impl=None, n_minibatches=1):
         if impl not in (None, "hip", "torch"):
             raise ValueError(f"PPOSolver: impl={impl!r} (None, 'hip' or 'torch')")
+        if not 1 <= int(n_minibatches) <= MAX_MINIBATCHES:
+            raise ValueError(f"PPOSolver: n_minibatches={n_minibatches} (1..{MAX_MINIBATCHES})")
+        self.n_minibatches = int(n_minibatches)
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         dev = torch.device(device)
@@ -160,6 +219,10 @@ class PPOSolver(Algorithm):
         if impl == "hip" and why:
             raise ValueError(f"PPOSolver(impl='hip'): {why}")
         self.impl_active = "torch" if impl == "torch" or why else "hip"
+        self.shuffle_calls = 0  # shuffled passes so far: the shuffle's Philox counter (the HIP path's device copy: _shuffle_counter)
+        self.last_perm = None   # the last pass's order (HIP: device int32 [B], the first n entries; torch: int64 [n])
+        if self.impl_active == "torch" and self.n_minibatches > 1:
+            self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if self.impl_active == "hip":
             D, H, _, A = _dims(self.actor_network)
             self.dims = (D, H, A)
@@ -175,6 +238,8 @@ class PPOSolver(Algorithm):
                 for p, g in zip(_params6(net), self._grads[net]):
                     p.grad = g
             self._per_batch = {}
+            self._per_shuffle = {}
+            self._shuffle_counter = torch.zeros(1, dtype=torch.int64, device=dev)  # shuffle_calls, on the device
             self._arrays()
             # the Categorical draws: Philox of (seed, calls so far, row)
             self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -241,6 +306,8 @@ class PPOSolver(Algorithm):
         if n_rows is not None and not (torch.is_tensor(n_rows) and n_rows.device == self.device
                                        and n_rows.dtype == torch.int64 and n_rows.numel() == 1):
             raise ValueError("n_rows: an int64 tensor [1] on the solver's device")
+        if self.n_minibatches > 1:
+            return self._hip_update_minibatches(s, a, ret, adv, old, B, n_rows)
         ws, loss_abs, loss_mean = self._buffers(B)
         fn, count = ("rth_ppo_grads", ()) if n_rows is None else ("rth_ppo_grads_n", (ptr(n_rows),))
         given = ()
@@ -256,6 +323,53 @@ class PPOSolver(Algorithm):
             self.hip_launches += 3
         self.last_loss = loss_mean.view(())
         return loss_abs
+
+    def _shuffle_buffers(self, B):
+        """the minibatch copy of a batch of capacity B (K slices of pitch Mcap), its row counts, the
+        permutation, |loss| in that layout and the shuffle's workspace: persistent, so a captured
+        update replays"""
+        if B not in self._per_shuffle:
+            K, D = self.n_minibatches, self.dims[0]
+            if K > B or B > MAX_SHUFFLE_ROWS:
+                raise ValueError(f"PPOSolver: n_minibatches={K} needs a batch capacity in {K}..{MAX_SHUFFLE_ROWS}, "
+                                 f"got {B}")
+            size = _lib.lib().rth_ppo_shuffle_workspace(B)
+            if size <= 0:
+                _lib.check(-1, "rth_ppo_shuffle_workspace")
+            Mcap = -(-B // K)
+            z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self.device)
+            m = dict(Mcap=Mcap, s=z((K * Mcap, D)), a=z(K * Mcap, torch.int64), ret=z(K * Mcap), adv=z(K * Mcap),
+                     logp=z(K * Mcap), n=z(K, torch.int64), perm=z(B, torch.int32), loss_abs=z(K * Mcap),
+                     ws=z(size // 8, torch.int64))
+            self._per_shuffle[B] = m
+        return self._per_shuffle[B]
+
+    def _hip_update_minibatches(self, s, a, ret, adv, old, B, n_rows):
+        D, H, A = self.dims
+        K = self.n_minibatches
+        mb = self._shuffle_buffers(B)
+        Mcap = mb["Mcap"]
+        ws, _, loss_mean = self._buffers(Mcap)
+        fn = "rth_ppo_grads_n" if adv is None else "rth_ppo_grads_adv"
+        for _ in range(self.k_epochs):
+            call("rth_ppo_shuffle", ptr(s), s.stride(0), ptr(a), ptr(ret), ptr(adv), ptr(old), B, ptr(n_rows), D, K,
+                 self.seed, ptr(self._shuffle_counter), None, ptr(mb["s"]), ptr(mb["a"]), ptr(mb["ret"]),
+                 None if adv is None else ptr(mb["adv"]), ptr(mb["logp"]), ptr(mb["n"]), ptr(mb["perm"]), ptr(mb["ws"]),
+                 stream_ptr())
+            self.shuffle_calls += 1
+            for m in range(K):
+                r = slice(m * Mcap, (m + 1) * Mcap)
+                given = () if adv is None else (ptr(mb["adv"][r]),)
+                p = self._arrays()
+                call(fn, p["actor"], p["value"], ptr(mb["s"][r]), D, ptr(mb["a"][r]), ptr(mb["ret"][r]), *given,
+                     ptr(mb["logp"][r]), Mcap, D, H, A, float(self.eps_clip), VF_COEF, ENT_COEF, p["actor_grads"],
+                     p["value_grads"], ptr(mb["loss_abs"][r]), ptr(loss_mean), ptr(ws), ptr(mb["n"][m:]), stream_ptr())
+                self.actor_optimizer.step()
+                self.value_optimizer.step()
+            self.hip_launches += 1 + 3 * K
+        self.last_perm = mb["perm"]
+        self.last_loss = loss_mean.view(())
+        return mb["loss_abs"]
 
     def _hip_act(self, states, uniforms, return_probs):
         D, H, A = self.dims
@@ -285,20 +399,48 @@ class PPOSolver(Algorithm):
         states = self._tensor(states, torch.float32)
         rewards = self._tensor(rewards, torch.float32)
         logprobs = self._tensor(logprobs, torch.float32)
+        if self.n_minibatches > 1:
+            return self._torch_update_minibatches(states, actions, rewards, logprobs, given)
         for _ in range(self.k_epochs):
-            new_logprobs, state_values, dist_entropy = self._evaluate_policy(states, actions)
-            ratios = torch.exp(new_logprobs - logprobs.detach())
-            advantages = rewards - state_values.detach() if given is None else given
-            surr1 = ratios * advantages
-            surr2 = torch.clamp(ratios, 1 - self.eps_clip, 1 + self.eps_clip) * advantages
-            loss = -torch.min(surr1, surr2) + VF_COEF * F.mse_loss(state_values, rewards) - ENT_COEF * dist_entropy
-            self.actor_optimizer.zero_grad()
-            self.value_network.zero_grad()
-            loss.mean().backward()
-            self.actor_optimizer.step()
-            self.value_optimizer.step()
+            loss = self._torch_step(states, actions, rewards, logprobs, given)
         self.last_loss = loss.detach().mean()
         return loss.detach().abs()
+
+    def _torch_step(self, states, actions, rewards, logprobs, given):
+        """one optimiser step on these rows; their loss"""
+        new_logprobs, state_values, dist_entropy = self._evaluate_policy(states, actions)
+        ratios = torch.exp(new_logprobs - logprobs.detach())
+        advantages = rewards - state_values.detach() if given is None else given
+        surr1 = ratios * advantages
+        surr2 = torch.clamp(ratios, 1 - self.eps_clip, 1 + self.eps_clip) * advantages
+        loss = -torch.min(surr1, surr2) + VF_COEF * F.mse_loss(state_values, rewards) - ENT_COEF * dist_entropy
+        self.actor_optimizer.zero_grad()
+        self.value_network.zero_grad()
+        loss.mean().backward()
+        self.actor_optimizer.step()
+        self.value_optimizer.step()
+        return loss
+
+    def _torch_update_minibatches(self, states, actions, rewards, logprobs, given):
+        """the HIP path's schedule on the reference's formulation: per pass minibatch_perm's order
+        and one step per minibatch; |loss| in the HIP path's layout [K * Mcap] (Mcap = M here: the
+        rows are the capacity), NaN where a slice has no row"""
+        K, n = self.n_minibatches, states.shape[0]
+        M = -(-n // K)
+        for _ in range(self.k_epochs):
+            perm, sizes = minibatch_perm(self.seed, self.shuffle_calls, n, K)
+            self.shuffle_calls += 1
+            if int(sizes.min()) == 0:
+                raise ValueError(f"PPOSolver(impl='torch'): {n} rows in {K} minibatches of {M} leave a minibatch empty")
+            out = torch.full((K * M,), float("nan"), device=self.device)
+            for m in range(K):
+                rows = torch.as_tensor(perm[m * M:m * M + int(sizes[m])], device=self.device)
+                loss = self._torch_step(states[rows], actions[rows], rewards[rows], logprobs[rows],
+                                        None if given is None else given[rows])
+                out[m * M:m * M + len(rows)] = loss.detach().abs()
+        self.last_perm = torch.as_tensor(perm, device=self.device)
+        self.last_loss = loss.detach().mean()
+        return out
 
     # ------------------------------------------------------------------ public
     def update_device(self, batch, weights=None, n_rows=None):
@@ -309,7 +451,13 @@ class PPOSolver(Algorithm):
         (rth_ppo_grads_n; buffers are kept per capacity B, and |loss| beyond the count is stale).
         The torch path reads n_rows on the host and slices: the yardstick only.  A fifth column,
         the advantages, is taken as given where the reference forms returns - values (GAE:
-        ppo_actors.finish_gae); the value loss still uses the returns (rth_ppo_grads_adv)."""
+        ppo_actors.finish_gae); the value loss still uses the returns (rth_ppo_grads_adv).
+
+        n_minibatches = K > 1 (the class docstring): the result is the last pass's |loss| in minibatch
+        layout [K * Mcap], Mcap = ceil(B / K): row m * Mcap + j is batch row last_perm[m * M + j] with
+        M = ceil(n / K), and rows beyond a minibatch's count are stale.  solver.last_perm is that
+        pass's permutation (on the device, its first n entries), last_loss the last minibatch's mean,
+        and shuffle_calls has advanced by k_epochs."""
         if len(batch) not in (4, 5):
             raise ValueError("batch: (states, actions, returns, old log-probabilities[, advantages])")
         if self.impl_active == "hip":

@@ -34,6 +34,12 @@ update_device on the 5-column batch (rth_ppo_grads_adv): horizon + 1 (+ 1 with n
 advantages' normalisation) + 3 k_epochs ABI calls.  Many envs on short rollouts -- 64 x 32 -- is
 what that is for.  None leaves everything above as it is.
 
+PpoLoopConfig.n_minibatches = K > 1 makes each of the k_epochs a shuffled pass over the batch in K
+minibatches with one optimiser step each (ppo.PPOSolver: rth_ppo_shuffle draws the order on the
+device from its own device counter, so a replayed graph reshuffles): step 3 is then k_epochs x
+(1 + 3 K) ABI calls.  K may not exceed the fewest rows a batch can hold (n_actors, or n_actors *
+horizon with GAE), so no minibatch is ever empty.
+
 The loop needs PPO's fused kernels (PPOSolver.impl_active == "hip"): without them it refuses to
 construct -- there is no torch fallback here.  It is not a device_loop.OneStreamLoop, which is
 replay-shaped (rows flow into a replay, a batch is sampled out of it).
@@ -43,7 +49,7 @@ from typing import Optional
 
 import torch
 
-from .ppo import PPOSolver
+from .ppo import MAX_MINIBATCHES, MAX_SHUFFLE_ROWS, PPOSolver
 from .ppo_actors import ENVS, VecPpoActors
 from .solver import Box, Discrete
 
@@ -61,6 +67,7 @@ class PpoLoopConfig:
     seed: int = 0
     gae_lambda: Optional[float] = None  # None: the reference's estimator; else GAE(lambda), any horizon >= 1
     normalize_adv: bool = False        # GAE only: the batch's advantages to mean 0, std 1
+    n_minibatches: int = 1             # K > 1: every epoch is a shuffled pass of K optimiser steps (ppo.PPOSolver)
 
 
 class PpoLoop:
@@ -82,17 +89,29 @@ class PpoLoop:
         if not self.gae and cfg.horizon < self.max_episode_steps:
             raise ValueError(f"PpoLoopConfig.horizon {cfg.horizon} < max_episode_steps {self.max_episode_steps}: an "
                              "iteration must let every env finish an episode, or a batch could be empty")
+        K = int(cfg.n_minibatches)
+        if not 1 <= K <= MAX_MINIBATCHES:
+            raise ValueError(f"PpoLoopConfig.n_minibatches {cfg.n_minibatches}: 1..{MAX_MINIBATCHES}")
+        least = cfg.n_actors * cfg.horizon if self.gae else cfg.n_actors  # the fewest rows a batch can hold
+        if K > least:
+            raise ValueError(f"PpoLoopConfig.n_minibatches {K}: a batch can hold as few as {least} rows, and no "
+                             "minibatch may be empty")
         torch.manual_seed(cfg.seed)
         self.solver = PPOSolver(Box(-1.0, 1.0, (obs_dim,)), Discrete(num_actions), k_epochs=cfg.k_epochs,
-                                eps_clip=cfg.eps_clip, learning_rate=cfg.learning_rate, device=self.device, impl=impl)
+                                eps_clip=cfg.eps_clip, learning_rate=cfg.learning_rate, device=self.device, impl=impl,
+                                n_minibatches=K)
         if self.solver.impl_active != "hip":
             raise RuntimeError("PpoLoop runs on PPO's fused kernels: the solver's active path is "
                                f"{self.solver.impl_active!r} (impl={impl!r}); there is no torch fallback")
         self.actors = VecPpoActors(cfg.env, cfg.n_actors, cfg.horizon, seed=cfg.seed,
                                    max_episode_steps=self.max_episode_steps, device=self.device,
                                    cap=cfg.horizon if self.gae else None)  # GAE: no carry
+        if K > 1 and self.actors.N * self.actors.cap > MAX_SHUFFLE_ROWS:
+            raise ValueError(f"PpoLoopConfig.n_minibatches {K}: the batch capacity n_actors * cap = "
+                             f"{self.actors.N * self.actors.cap} is above the shuffle's {MAX_SHUFFLE_ROWS} rows")
         self.iterations = self.env_steps = self.updates = 0
-        self.last_loss_abs = None  # the last update's |loss| [N * cap]: rows beyond the batch are stale
+        # the last update's |loss| [N * cap]: rows beyond the batch are stale (K > 1: update_device's minibatch layout)
+        self.last_loss_abs = None
         self._graph = None
 
     # ------------------------------------------------------------------ one iteration
@@ -111,10 +130,11 @@ class PpoLoop:
         """the host mirrors, as (object, attribute, what one iteration adds), of what _body()
         advances on the device: recording it moves them, so capture() puts them back, and
         iteration() advances them after every replay"""
-        act, T = self.actors, self.cfg.horizon
+        act, T, K = self.actors, self.cfg.horizon, self.solver.n_minibatches
         return [(act, "pushes", T), (act, "launches", T), (act, "finishes", 1),
                 (act, "normalizes", int(self.gae and self.cfg.normalize_adv)),
-                (self.solver, "hip_launches", 3 * self.cfg.k_epochs)]
+                (self.solver, "hip_launches", self.cfg.k_epochs * (3 * K + int(K > 1))),
+                (self.solver, "shuffle_calls", self.cfg.k_epochs * int(K > 1))]
 
     def iteration(self):
         """one iteration on the current stream; never synchronises with the host"""
