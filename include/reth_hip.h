@@ -1180,6 +1180,34 @@ int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *
 int rth_ppo_gae_finish(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
                        float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
                        float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream);
+/* rth_ppo_actor_step that also records why an episode ended and what it ended on.  With the row it
+ * stores (0 <= fill[i] < cap; a dropped row writes neither column):
+ *   seg_trunc[row] = (steps >= max_episode_steps && !terminal) ? 1 : 0    [N, cap] f32
+ * where `terminal` is the dynamics' own end: an end with both causes on one step is terminal, not
+ * truncated.  On a truncated row only, seg_term_s[row * D .. + D) ([N, cap, D] f32) gets the
+ * observation of the post-dynamics state, taken before the reset draw replaces it; other rows of
+ * seg_term_s are not written.  Every other output -- action, logprob, state, stats, cur_obs, the
+ * five segment columns, fill / complete / dropped -- equals rth_ppo_actor_step's bit for bit.  One
+ * launch, no atomics, graph-capturable; arguments are checked before anything is launched. */
+int rth_ppo_actor_step_tl(const rth_ppo_actor_args *args, float *seg_trunc_dev, float *seg_term_s_dev, void *stream);
+/* rth_ppo_gae_finish that bootstraps through time-limit ends.  Per env, after v_t and v_last, vterm_t
+ * = value(seg_term_s[t]) for the rows with seg_trunc[t] != 0, by the same forward, and the scan
+ * selects its operands:
+ *   nt    = 1 - done_t
+ *   nb    = trunc_t ? 1 : nt
+ *   nv    = trunc_t ? vterm_t : ((t == T-1) ? v_last : v_{t+1})
+ *   delta = (r_t + (gamma * nv) * nb) - v_t
+ *   run   = delta + ((gamma * lam) * nt) * run
+ *   adv_t = (float) run,   ret_t = (float) (run + (double) v_t)
+ * in fp64, every operation rounded once and none contracted.  The lambda-chain is still cut at every
+ * done row; a truncated row (done flags are 0 or 1) bootstraps from the value of the state its
+ * episode ended on.  With seg_trunc all zero every output equals rth_ppo_gae_finish's bit for bit;
+ * rows of seg_term_s whose seg_trunc is 0 are never read.  Row order, n_dev, the counters, the two
+ * launches and the checks are rth_ppo_gae_finish's; both new columns are required (not NULL). */
+int rth_ppo_gae_finish_tl(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
+                          float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
+                          float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, const float *seg_trunc_dev,
+                          const float *seg_term_s_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-resident continuous-control actors on DDPG's fused actor (csrc/ddpg_actor.hpp): one

@@ -325,6 +325,10 @@ SIGNATURES = {
     # the PPO actors, their rollout and its end (ppo_actor.hpp)
     "rth_ppo_env_reset": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),
     "rth_ppo_actor_step": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp]),
+    # ... with time-limit ends recorded by the step and bootstrapped through by the finish
+    "rth_ppo_actor_step_tl": (c_i32, [ctypes.POINTER(PpoActorArgs), c_vp, c_vp, c_vp]),
+    "rth_ppo_gae_finish_tl": (c_i32, [ctypes.POINTER(PpoActorArgs), ctypes.POINTER(c_vp), c_f64, c_f64, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rth_ppo_rollout_finish": (c_i32, [ctypes.POINTER(PpoActorArgs), c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # the CartPole actors on the MLP kernels (mlp_actor.hpp: adapters onto the step below)
     "rth_cartpole_reset": (c_i32, [ctypes.POINTER(MlpActorArgs), c_vp]),

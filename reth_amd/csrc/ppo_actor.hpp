@@ -61,7 +61,24 @@
 // in that launch writes fill, so every workgroup sums what the steps left; a second, small launch
 // (k_ppo_gae_clear) then sets fill[i] = 0 and both complete slots of env i = 0, and gen[i] += 1.
 // One launch would have workgroup k zero fill[k] while workgroup i > k may not have read it yet.
+//
+// Time-limit ends (rth_ppo_actor_step_tl, rth_ppo_gae_finish_tl): the same two kernels with a
+// compile-time flag, on two more columns.  The step also stores, with the row, seg_trunc [N, cap] =
+// (steps >= max_episode_steps && !terminal) -- both causes on one step: terminal -- and, on a
+// truncated row only, seg_term_s [N, cap, D] = the observation of the post-dynamics state
+// (env_store_obs before env_reset_draw); everything else is the step's, bit for bit.  The finish
+// lists the truncated rows of its env in increasing t, runs the same forward over that list in
+// tiles of kPpoRows (vterm_t = value(seg_term_s[t]); rows with trunc 0 are never read), and the scan
+// selects its operands:
+//   nt    = 1 - done_t
+//   nb    = trunc_t ? 1 : nt
+//   nv    = trunc_t ? vterm_t : (t == T-1 ? v_last : v_{t+1})
+//   delta = (r_t + (gamma * nv) * nb) - v_t
+//   run   = delta + ((gamma * lam) * nt) * run        the lambda-chain is still cut at every done row
+// so a truncated row bootstraps from the value of the state its episode ended on, and trunc = 0
+// everywhere is the scan above, operation for operation.
 #pragma once
+#include <type_traits>
 #include "env_actor.hpp"
 #include "ppo.hpp"
 
@@ -91,6 +108,14 @@ struct PpoActor {
   int cap, max_steps;
 };
 
+// the argument block of the time-limit variants (rth_ppo_actor_step_tl, rth_ppo_gae_finish_tl): two more columns
+struct PpoActorTl : PpoActor {
+  float *seg_trunc;   // [N, cap]: 1 where the time limit alone ended the row's episode
+  float *seg_term_s;  // [N, cap, D]: a truncated row's final observation; other rows are never written or read
+};
+template <bool TL>
+using PpoActorOf = std::conditional_t<TL, PpoActorTl, PpoActor>;
+
 __device__ __forceinline__ int ppo_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 template <int ENV>
@@ -113,8 +138,10 @@ __global__ __launch_bounds__(256) void k_ppo_env_reset(PpoActor a) {
   a.dropped[i] = 0;
 }
 
-template <int ENV>
-__global__ __launch_bounds__(kPpoThreads) void k_ppo_actor_step(PpoActor a) {
+// TL: the step of rth_ppo_actor_step_tl -- the same code plus the row's seg_trunc and, on a truncated
+// row, seg_term_s (the header's "Time-limit ends").
+template <int ENV, bool TL>
+__global__ __launch_bounds__(kPpoThreads) void k_ppo_actor_step(PpoActorOf<TL> a) {
   constexpr int D = EnvSpec<ENV>::D, A = EnvSpec<ENV>::A, LD = env_ld(D);
   static_assert(D <= kPpoMaxD && A >= kPpoMinA && A <= kPpoMaxA, "the env's shape is one ppo.hpp builds");
   __shared__ __align__(16) PpoActSmem s;
@@ -152,7 +179,13 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_actor_step(PpoActor a) {
     }
     const float lp = s.dist.logp[tid][act];
     float rew;
-    const bool done = env_dynamics<ENV>(st, act, &rew) | (steps >= a.max_steps);
+    const bool terminal = env_dynamics<ENV>(st, act, &rew);
+    const bool done = terminal | (steps >= a.max_steps);
+    [[maybe_unused]] const bool trunc = !terminal & (steps >= a.max_steps);  // both causes on one step: terminal
+    [[maybe_unused]] __align__(16) float term[LD];
+    if constexpr (TL) {
+      if (trunc) env_store_obs<ENV>(term, st);  // what the episode ended on, before the reset draw replaces it
+    }
     const double ret = radd(run[0], (double)rew);
     if (done) {
       env_reset_draw<ENV>(a.seed, i, t, st);
@@ -177,6 +210,13 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_actor_step(PpoActor a) {
       a.seg_r[row] = rew;
       a.seg_done[row] = done ? 1.0f : 0.0f;
       a.seg_logp[row] = lp;
+      if constexpr (TL) {
+        a.seg_trunc[row] = trunc ? 1.0f : 0.0f;
+        if (trunc) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) a.seg_term_s[row * D + k] = term[k];
+        }
+      }
       a.fill[i] = f + 1;
       if (done) a.complete[(int64_t)slot * N + i] = f + 1;
     } else {
@@ -283,21 +323,39 @@ struct PpoGaeSmem {
   float r[kPpoMaxCap], dn[kPpoMaxCap], v[kPpoMaxCap + 4];
   int64_t red[kPpoThreads];
 };
+// ... and of the time-limit variant: vt[t] the value of truncated row t's final observation, tl the
+// truncated rows in increasing t (a row index fits 16 bits: cap <= 4096).  A row's truncation flag is
+// the sign bit of its dn (done flags are 0 or 1), so it costs no column: 24 KB more, 122 KB of 160.
+struct PpoGaeTlSmem : PpoGaeSmem {
+  float vt[kPpoMaxCap];
+  uint16_t tl[kPpoMaxCap];
+};
+static_assert(kPpoMaxCap <= 65536 && sizeof(PpoGaeTlSmem) <= 160 * 1024, "a CU's LDS holds the time-limit finish");
 
-__global__ __launch_bounds__(kPpoThreads) void k_ppo_gae_finish(PpoActor a, DenseNet va, int D, int LD, double gamma,
-                                                                double lam, float *__restrict__ bs,
+// TL: the finish of rth_ppo_gae_finish_tl (the header's "Time-limit ends").  Without the flag the
+// kernel, its LDS and its code are rth_ppo_gae_finish's.
+template <bool TL>
+__global__ __launch_bounds__(kPpoThreads) void k_ppo_gae_finish(PpoActorOf<TL> a, DenseNet va, int D, int LD,
+                                                                double gamma, double lam, float *__restrict__ bs,
                                                                 int64_t *__restrict__ ba, float *__restrict__ bret,
                                                                 float *__restrict__ badv, float *__restrict__ bv,
                                                                 float *__restrict__ blogp,
                                                                 int64_t *__restrict__ n_dev) {
-  __shared__ __align__(16) PpoGaeSmem s;
+  __shared__ __align__(16) std::conditional_t<TL, PpoGaeTlSmem, PpoGaeSmem> s;
   const int tid = threadIdx.x, cap = a.cap;
   const int64_t i = blockIdx.x, N = a.N, base = i * cap;
   const int m = ppo_clampi(a.fill[i], 0, cap);  // no launch of this kernel writes fill: k_ppo_gae_clear does
   int64_t acc = 0;  // the batch offset: an integer sum, so its order is free
   for (int64_t k = tid; k < i; k += kPpoThreads) acc += ppo_clampi(a.fill[k], 0, cap);
   s.red[tid] = acc;
-  for (int t = tid; t < m; t += kPpoThreads) s.r[t] = a.seg_r[base + t], s.dn[t] = a.seg_done[base + t];
+  for (int t = tid; t < m; t += kPpoThreads) {
+    s.r[t] = a.seg_r[base + t];
+    float dn = a.seg_done[base + t];
+    if constexpr (TL) {
+      if (a.seg_trunc[base + t] != 0.0f) dn = -fabsf(dn);  // (-0 where done is 0: the sign bit alone is read)
+    }
+    s.dn[t] = dn;
+  }
   if (m > 0) ppo_stage_net(va, D, 1, s.value);  // (uniform)
   __syncthreads();
   for (int st = kPpoThreads / 2; st > 0; st >>= 1) {
@@ -319,13 +377,60 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo_gae_finish(PpoActor a, Dens
     ppo_forward_rows(s.value, s.x, D, 1, s.rv);
     if (tid < kPpoRows && r0 + tid <= m) s.v[r0 + tid] = s.rv.z[tid][0];
   }
+  if constexpr (TL) {
+    // the truncated rows, compacted in increasing t: lane tid counts those of its own run of `per`
+    // rows, red becomes the counts' running sum (every lane has read `off`), the lane lists its rows
+    const int per = (m + kPpoThreads - 1) / kPpoThreads;
+    const int t0 = ppo_clampi(tid * per, 0, m), t1 = ppo_clampi(t0 + per, 0, m);
+    int mine = 0;
+    for (int t = t0; t < t1; ++t) mine += (int)signbit(s.dn[t]);
+    __syncthreads();
+    s.red[tid] = mine;
+    __syncthreads();
+    if (tid == 0) {
+      int64_t sum = 0;
+      for (int k = 0; k < kPpoThreads; ++k) {
+        const int64_t c = s.red[k];
+        s.red[k] = sum;
+        sum += c;
+      }
+    }
+    __syncthreads();
+    int at = (int)s.red[tid];
+    for (int t = t0; t < t1; ++t)
+      if (signbit(s.dn[t])) s.tl[at++] = (uint16_t)t;
+    if (tid == kPpoThreads - 1) s.red[tid] = at;  // the total: the last lane's start plus its count
+    __syncthreads();
+    const int n_tl = (int)s.red[kPpoThreads - 1];  // 0..m (uniform)
+    // their values: the same forward on the final observations, a tile of the list at a time
+    for (int c0 = 0; c0 < n_tl; c0 += kPpoRows) {
+      __syncthreads();
+      for (int e = tid; e < kPpoRows * kPpoMaxD; e += kPpoThreads) {
+        const int r = e / kPpoMaxD, k = e % kPpoMaxD, q = c0 + r;
+        float x = 0.0f;
+        if (k < D && q < n_tl) x = a.seg_term_s[(base + s.tl[q]) * D + k];
+        s.x[r][k] = x;
+      }
+      ppo_forward_rows(s.value, s.x, D, 1, s.rv);
+      if (tid < kPpoRows && c0 + tid < n_tl) s.vt[s.tl[c0 + tid]] = s.rv.z[tid][0];
+    }
+  }
   __syncthreads();
   if (tid == 0) {  // the scan: serial, fp64, every operation rounded once
     const double gl = rmul(gamma, lam);
     double run = 0.0;
     for (int t = m - 1; t >= 0; --t) {
-      const double nt = rsub(1.0, (double)s.dn[t]), vt = (double)s.v[t];
-      const double delta = rsub(radd((double)s.r[t], rmul(rmul(gamma, (double)s.v[t + 1]), nt)), vt);
+      double nt, vt, delta;
+      if constexpr (TL) {  // selects: a row that is not truncated takes the operands of the scan without the flag
+        const float dn = s.dn[t];
+        const bool tr = signbit(dn);
+        nt = rsub(1.0, (double)fabsf(dn)), vt = (double)s.v[t];
+        const double nb = tr ? 1.0 : nt, nv = tr ? (double)s.vt[t] : (double)s.v[t + 1];
+        delta = rsub(radd((double)s.r[t], rmul(rmul(gamma, nv), nb)), vt);
+      } else {
+        nt = rsub(1.0, (double)s.dn[t]), vt = (double)s.v[t];
+        delta = rsub(radd((double)s.r[t], rmul(rmul(gamma, (double)s.v[t + 1]), nt)), vt);
+      }
       run = radd(delta, rmul(rmul(gl, nt), run));
       s.r[t] = (float)run;
       s.dn[t] = (float)radd(run, vt);
@@ -390,7 +495,12 @@ inline const char *ppo_actor_check(const rth_ppo_actor_args *x, int what, PpoAct
 
 template <int ENV>
 inline void ppo_env_launch(bool step, const PpoActor &a, hipStream_t st) {
-  actor_launch<k_ppo_actor_step<ENV>, k_ppo_env_reset<ENV>, kPpoThreads>(step, a, st);
+  actor_launch<k_ppo_actor_step<ENV, false>, k_ppo_env_reset<ENV>, kPpoThreads>(step, a, st);
+}
+
+template <int ENV>
+inline void ppo_step_tl_launch(const PpoActorTl &a, hipStream_t st) {
+  hipLaunchKernelGGL((k_ppo_actor_step<ENV, true>), dim3(dense_grid(a.N)), dim3(kPpoThreads), 0, st, a);
 }
 
 // The body of the reset and the step: the checks, then the env's kernel.
@@ -407,6 +517,36 @@ inline int ppo_actor_run(const char *fn, const rth_ppo_actor_args *x, bool step,
   return RTH_OK;
 }
 
+// The body of the two GAE finishes: the checks, the finish (TL: with the time-limit columns), the counters.
+template <bool TL>
+inline int ppo_gae_run(const char *fn, const rth_ppo_actor_args *args, const float *const *value, double gamma,
+                       double lam, float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev,
+                       float *batch_adv_dev, float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev,
+                       const float *seg_trunc_dev, const float *seg_term_s_dev, void *stream) {
+  PpoActorOf<TL> a{};
+  const char *bad = ppo_actor_check(args, kPpoGae, &a);
+  RTH_REQUIRE(!bad, "%s: %s", fn, bad);
+  DenseNet va;
+  RTH_REQUIRE(dense_net(value, &va), "%s: NULL value network parameter", fn);
+  RTH_REQUIRE(batch_s_dev && batch_a_dev && batch_ret_dev && batch_adv_dev && batch_v_dev && batch_logprob_dev && n_dev,
+              "%s: NULL batch buffer", fn);
+  RTH_REQUIRE(gamma >= 0.0 && gamma <= 1.0 && lam >= 0.0 && lam <= 1.0, "%s: bad gamma %g or lambda %g (0..1)", fn,
+              gamma, lam);
+  if constexpr (TL) {
+    RTH_REQUIRE(seg_trunc_dev && seg_term_s_dev, "%s: NULL time-limit column", fn);
+    a.seg_trunc = const_cast<float *>(seg_trunc_dev), a.seg_term_s = const_cast<float *>(seg_term_s_dev);  // read only
+  }
+  const int D = (int)args->D;
+  hipLaunchKernelGGL((k_ppo_gae_finish<TL>), dim3((unsigned)a.N), dim3(kPpoThreads), 0, as_stream(stream), a, va, D,
+                     env_ld(D), gamma, lam, batch_s_dev, batch_a_dev, batch_ret_dev, batch_adv_dev, batch_v_dev,
+                     batch_logprob_dev, n_dev);
+  RTH_LAUNCHED();
+  hipLaunchKernelGGL(k_ppo_gae_clear, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, as_stream(stream),
+                     static_cast<const PpoActor &>(a));
+  RTH_LAUNCHED();
+  return RTH_OK;
+}
+
 }  // namespace rth
 
 extern "C" {
@@ -417,6 +557,22 @@ int rth_ppo_env_reset(const rth_ppo_actor_args *args, void *stream) {
 
 int rth_ppo_actor_step(const rth_ppo_actor_args *args, void *stream) {
   return rth::ppo_actor_run("rth_ppo_actor_step", args, true, stream);
+}
+
+int rth_ppo_actor_step_tl(const rth_ppo_actor_args *args, float *seg_trunc_dev, float *seg_term_s_dev, void *stream) {
+  using namespace rth;
+  PpoActorTl a{};
+  const char *bad = ppo_actor_check(args, kPpoStep, &a);
+  RTH_REQUIRE(!bad, "rth_ppo_actor_step_tl: %s", bad);
+  RTH_REQUIRE(seg_trunc_dev && seg_term_s_dev, "rth_ppo_actor_step_tl: NULL time-limit column");
+  a.seg_trunc = seg_trunc_dev, a.seg_term_s = seg_term_s_dev;
+  switch (args->env) {
+    case RTH_ENV_CARTPOLE: ppo_step_tl_launch<RTH_ENV_CARTPOLE>(a, as_stream(stream)); break;
+    case RTH_ENV_ACROBOT: ppo_step_tl_launch<RTH_ENV_ACROBOT>(a, as_stream(stream)); break;
+    default: ppo_step_tl_launch<RTH_ENV_MOUNTAINCAR>(a, as_stream(stream));
+  }
+  RTH_LAUNCHED();
+  return RTH_OK;
 }
 
 int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *batch_s_dev, int64_t *batch_a_dev,
@@ -438,24 +594,17 @@ int rth_ppo_rollout_finish(const rth_ppo_actor_args *args, double gamma, float *
 int rth_ppo_gae_finish(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
                        float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
                        float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, void *stream) {
-  using namespace rth;
-  PpoActor a;
-  const char *bad = ppo_actor_check(args, kPpoGae, &a);
-  RTH_REQUIRE(!bad, "rth_ppo_gae_finish: %s", bad);
-  DenseNet va;
-  RTH_REQUIRE(dense_net(value, &va), "rth_ppo_gae_finish: NULL value network parameter");
-  RTH_REQUIRE(batch_s_dev && batch_a_dev && batch_ret_dev && batch_adv_dev && batch_v_dev && batch_logprob_dev && n_dev,
-              "rth_ppo_gae_finish: NULL batch buffer");
-  RTH_REQUIRE(gamma >= 0.0 && gamma <= 1.0 && lam >= 0.0 && lam <= 1.0,
-              "rth_ppo_gae_finish: bad gamma %g or lambda %g (0..1)", gamma, lam);
-  const int D = (int)args->D;
-  hipLaunchKernelGGL(k_ppo_gae_finish, dim3((unsigned)a.N), dim3(kPpoThreads), 0, as_stream(stream), a, va, D,
-                     env_ld(D), gamma, lam, batch_s_dev, batch_a_dev, batch_ret_dev, batch_adv_dev, batch_v_dev,
-                     batch_logprob_dev, n_dev);
-  RTH_LAUNCHED();
-  hipLaunchKernelGGL(k_ppo_gae_clear, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, as_stream(stream), a);
-  RTH_LAUNCHED();
-  return RTH_OK;
+  return rth::ppo_gae_run<false>("rth_ppo_gae_finish", args, value, gamma, lam, batch_s_dev, batch_a_dev, batch_ret_dev,
+                                 batch_adv_dev, batch_v_dev, batch_logprob_dev, n_dev, nullptr, nullptr, stream);
+}
+
+int rth_ppo_gae_finish_tl(const rth_ppo_actor_args *args, const float *const *value, double gamma, double lam,
+                          float *batch_s_dev, int64_t *batch_a_dev, float *batch_ret_dev, float *batch_adv_dev,
+                          float *batch_v_dev, float *batch_logprob_dev, int64_t *n_dev, const float *seg_trunc_dev,
+                          const float *seg_term_s_dev, void *stream) {
+  return rth::ppo_gae_run<true>("rth_ppo_gae_finish_tl", args, value, gamma, lam, batch_s_dev, batch_a_dev,
+                                batch_ret_dev, batch_adv_dev, batch_v_dev, batch_logprob_dev, n_dev, seg_trunc_dev,
+                                seg_term_s_dev, stream);
 }
 
 }  // extern "C"

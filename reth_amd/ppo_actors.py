@@ -29,6 +29,12 @@ Every stored row of every env enters the batch, with its advantage and its value
 columns, and the segments are empty afterwards: there is no carry, so cap = horizon rows hold a
 rollout (the keyword cap) and any horizon >= 1 runs.
 
+time_limit_bootstrap=True keeps two more columns per segment -- seg_trunc (1 where the time limit
+alone ended the row's episode) and seg_term_s (such a row's final observation, which the reset draw
+has replaced in cur_obs by the time a finish runs) -- written by rth_ppo_actor_step_tl, and finish_gae
+then bootstraps every truncated row from the value of the state it ended on
+(rth_ppo_gae_finish_tl).  finish() does not read them.
+
 HostRollout restates the store, the finishes and the carry in numpy with the kernel's arithmetic in
 its order: the oracle of the GPU tests, testable without a GPU.
 """
@@ -54,11 +60,15 @@ class VecPpoActors(VecEnvActors):
     finish() calls, which sizes the segments (module docstring).  cur_obs rows are obs_dim rounded
     up to 4 floats (the pad stays 0).  Episode statistics in int64 (episode_stats) and fp64 returns
     (return_stats).  max_episode_steps defaults to the env's TimeLimit.  cap: the rows per env's
-    segment, 1..4096; None is finish()'s rule, horizon + max_episode_steps - 1."""
+    segment, 1..4096; None is finish()'s rule, horizon + max_episode_steps - 1.
+    time_limit_bootstrap: step() records time-limit ends (seg_trunc, seg_term_s) and finish_gae()
+    bootstraps through them (module docstring)."""
     _envs = ENVS
 
-    def __init__(self, env, n_actors, horizon, seed=0, max_episode_steps=None, device=None, cap=None):
+    def __init__(self, env, n_actors, horizon, seed=0, max_episode_steps=None, device=None, cap=None,
+                 time_limit_bootstrap=False):
         self.horizon = int(horizon)
+        self.time_limit_bootstrap = bool(time_limit_bootstrap)
         super().__init__(env, n_actors, seed, max_episode_steps, device, horizon=self.horizon)
         self.num_actions = ENVS[env][2]
         if cap is None:
@@ -77,6 +87,9 @@ class VecPpoActors(VecEnvActors):
         self.seg_r, self.seg_done, self.seg_logp = (z((N, cap), torch.float32) for _ in range(3))
         self.fill, self.gen, self.dropped = z((N,), torch.int32), z((N,), torch.int32), z((N,), torch.int64)
         self._complete = z((2, N), torch.int32)  # env i's live slot: gen[i] & 1
+        self.seg_trunc = self.seg_term_s = None
+        if self.time_limit_bootstrap:
+            self.seg_trunc, self.seg_term_s = z((N, cap), torch.float32), z((N, cap, D), torch.float32)
         # the batch a finish() writes, persistent: N * cap rows hold any rollout
         self.batch = [z((N * cap, D), torch.float32), z((N * cap,), torch.int64), z((N * cap,), torch.float32),
                       z((N * cap,), torch.float32)]
@@ -156,7 +169,10 @@ class VecPpoActors(VecEnvActors):
                                          and uniforms.dtype == torch.float64 and uniforms.numel() == self.N):
             raise ValueError("uniforms: a contiguous float64 device tensor [N]")
         args = self._args(self._params(solver_or_actor), action_in, uniforms)
-        call("rth_ppo_actor_step", _lib.ctypes.byref(args), stream_ptr())
+        if self.time_limit_bootstrap:
+            call("rth_ppo_actor_step_tl", _lib.ctypes.byref(args), ptr(self.seg_trunc), ptr(self.seg_term_s), stream_ptr())
+        else:
+            call("rth_ppo_actor_step", _lib.ctypes.byref(args), stream_ptr())
         self.launches += 1
         self.pushes += 1
 
@@ -195,14 +211,16 @@ class VecPpoActors(VecEnvActors):
         network (or a ppo.ValueNetwork) and its value of cur_obs as the bootstrap (gae() below is
         the arithmetic).  The segments are empty afterwards: no carry.  batch_v holds the rows'
         values.  normalize: one more call, rth_ppo_adv_normalize over the n rows.  Persistent
-        tensors, as finish()'s; rows at n and beyond are stale."""
+        tensors, as finish()'s; rows at n and beyond are stale.  With time_limit_bootstrap a row
+        whose seg_trunc is set bootstraps from the value of its seg_term_s row instead of nothing."""
         if self.batch_adv is None:
             self.batch_adv, self.batch_v = (self._alloc((self.N * self.cap,), torch.float32) for _ in range(2))
         args = self._args()
         s, a, ret, logp = self.batch
-        call("rth_ppo_gae_finish", _lib.ctypes.byref(args), self._value_params(solver_or_value), float(gamma),
-             float(lam), ptr(s), ptr(a), ptr(ret), ptr(self.batch_adv), ptr(self.batch_v), ptr(logp), ptr(self.n_dev),
-             stream_ptr())
+        tl = (ptr(self.seg_trunc), ptr(self.seg_term_s)) if self.time_limit_bootstrap else ()
+        call("rth_ppo_gae_finish_tl" if tl else "rth_ppo_gae_finish", _lib.ctypes.byref(args),
+             self._value_params(solver_or_value), float(gamma), float(lam), ptr(s), ptr(a), ptr(ret), ptr(self.batch_adv),
+             ptr(self.batch_v), ptr(logp), ptr(self.n_dev), *tl, stream_ptr())
         self.finishes += 1
         if normalize:
             call("rth_ppo_adv_normalize", ptr(self.batch_adv), self.N * self.cap, ptr(self.n_dev), stream_ptr())
@@ -210,13 +228,18 @@ class VecPpoActors(VecEnvActors):
         return [s, a, ret, logp, self.batch_adv], self.n_dev
 
 
-def gae(r, done, v, v_last, gamma, lam, dtype=np.float32):
+def gae(r, done, v, v_last, gamma, lam, dtype=np.float32, trunc=None, v_term=None):
     """the kernel's GAE(lambda) of ONE env's rows (csrc/ppo_actor.hpp): (adv, ret) float32 [T] from
     float32 rewards, done flags and values and the value v_last of the state behind the last row;
     fp64, every operation rounded once, in the kernel's order (dtype=np.float64: before the final
-    rounding)"""
+    rounding).  trunc [T] (nonzero: the time limit alone ended the row's episode) with v_term [T]
+    (the values of those rows' final observations; other entries are not read) is the scan of
+    rth_ppo_gae_finish_tl: a truncated row bootstraps from v_term[t], and the lambda-chain is cut at
+    every done row as before."""
     r, done, v = (np.asarray(x, np.float32).astype(np.float64) for x in (r, done, v))
     T = len(r)
+    if trunc is not None:
+        return _gae_tl(r, done, v, v_last, gamma, lam, dtype, np.asarray(trunc), np.asarray(v_term, np.float32))
     adv, ret = np.zeros(T, dtype), np.zeros(T, dtype)
     g = np.float64(gamma)
     gl = g * np.float64(lam)
@@ -227,6 +250,24 @@ def gae(r, done, v, v_last, gamma, lam, dtype=np.float32):
         run = delta + (gl * nt) * run
         adv[t], ret[t] = run, run + v[t]  # rounded once by the store
         nv = v[t]
+    return adv, ret
+
+
+def _gae_tl(r, done, v, v_last, gamma, lam, dtype, trunc, v_term):
+    """gae() with the truncation flags: the same operations on selected operands"""
+    T = len(r)
+    adv, ret = np.zeros(T, dtype), np.zeros(T, dtype)
+    g = np.float64(gamma)
+    gl = g * np.float64(lam)
+    nxt, run = np.float64(np.float32(v_last)), np.float64(0.0)
+    for t in range(T - 1, -1, -1):
+        nt = np.float64(1.0) - done[t]
+        nb = np.float64(1.0) if trunc[t] else nt
+        nv = np.float64(v_term[t]) if trunc[t] else nxt
+        delta = (r[t] + (g * nv) * nb) - v[t]
+        run = delta + (gl * nt) * run
+        adv[t], ret[t] = run, run + v[t]  # rounded once by the store
+        nxt = v[t]
     return adv, ret
 
 
@@ -262,11 +303,16 @@ class HostRollout:
         self.seg_r, self.seg_done, self.seg_logp = (np.zeros((N, cap), np.float32) for _ in range(3))
         self.fill, self.complete = np.zeros(N, np.int32), np.zeros(N, np.int32)
         self.dropped = np.zeros(N, np.int64)
+        # the time-limit columns (store(trunc=, term_s=)); term_s rows of other steps stay NaN
+        self.seg_trunc, self.seg_term_s = np.zeros((N, cap), np.float32), np.full((N, cap, D), np.nan, np.float32)
 
-    def store(self, s0, a, r, done, logp):
-        """one step's rows, one per env: s0 [N, D], the others [N]"""
+    def store(self, s0, a, r, done, logp, trunc=None, term_s=None):
+        """one step's rows, one per env: s0 [N, D], the others [N]; trunc [N] (the time limit alone
+        ended the episode) with term_s [N, D] (the final observations, read where trunc is set)"""
         s0 = np.asarray(s0, np.float32).reshape(self.N, self.D)
         a, r, done, logp = (np.asarray(v).reshape(self.N) for v in (a, r, done, logp))
+        if trunc is not None:
+            trunc, term_s = np.asarray(trunc).reshape(self.N), np.asarray(term_s, np.float32).reshape(self.N, self.D)
         for i in range(self.N):
             f = int(self.fill[i])
             if f >= self.cap:
@@ -274,6 +320,10 @@ class HostRollout:
                 continue
             self.seg_s[i, f], self.seg_a[i, f], self.seg_r[i, f] = s0[i], a[i], r[i]
             self.seg_done[i, f], self.seg_logp[i, f] = (1.0 if done[i] else 0.0), logp[i]
+            if trunc is not None:
+                self.seg_trunc[i, f] = 1.0 if trunc[i] else 0.0
+                if trunc[i]:
+                    self.seg_term_s[i, f] = term_s[i]
             self.fill[i] = f + 1
             if done[i]:
                 self.complete[i] = f + 1
@@ -299,15 +349,19 @@ class HostRollout:
         s, a, ret, logp = (np.concatenate(o) for o in out)
         return s, a, ret, logp, len(a)
 
-    def finish_gae(self, v, v_last, gamma, lam):
+    def finish_gae(self, v, v_last, gamma, lam, v_term=None):
         """(s [n, D], a [n], ret [n], logp [n], adv [n], n): every stored row of every env,
         env-major, then in time order, with gae() on the rows' values v [N, cap] and the bootstrap
-        values v_last [N]; the segments are empty afterwards"""
+        values v_last [N]; the segments are empty afterwards.  v_term [N, cap]: the values of
+        seg_term_s, read where seg_trunc is set -- gae() with the truncation flags."""
         v, v_last = np.asarray(v, np.float32).reshape(self.N, self.cap), np.asarray(v_last, np.float32).reshape(self.N)
+        if v_term is not None:
+            v_term = np.asarray(v_term, np.float32).reshape(self.N, self.cap)
         out = [[], [], [], [], []]
         for i in range(self.N):
             m = int(self.fill[i])
-            adv, ret = gae(self.seg_r[i, :m], self.seg_done[i, :m], v[i, :m], v_last[i], gamma, lam)
+            tl = {} if v_term is None else dict(trunc=self.seg_trunc[i, :m], v_term=v_term[i, :m])
+            adv, ret = gae(self.seg_r[i, :m], self.seg_done[i, :m], v[i, :m], v_last[i], gamma, lam, **tl)
             for o, col in zip(out, (self.seg_s[i, :m], self.seg_a[i, :m], ret, self.seg_logp[i, :m], adv)):
                 o.append(col.copy())
         self.fill[:], self.complete[:] = 0, 0

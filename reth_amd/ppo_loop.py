@@ -40,6 +40,12 @@ device from its own device counter, so a replayed graph reshuffles): step 3 is t
 (1 + 3 K) ABI calls.  K may not exceed the fewest rows a batch can hold (n_actors, or n_actors *
 horizon with GAE), so no minibatch is ever empty.
 
+PpoLoopConfig.bootstrap_time_limit (GAE only) removes the estimator's bias at time-limit ends: the
+step records which done rows the limit alone ended and the observation they ended on, and the finish
+bootstraps those rows from the value of that observation instead of treating them as terminal states
+of value 0 (ppo_actors' time_limit_bootstrap; rth_ppo_actor_step_tl, rth_ppo_gae_finish_tl).  The
+ABI calls per iteration are the same in number.
+
 The loop needs PPO's fused kernels (PPOSolver.impl_active == "hip"): without them it refuses to
 construct -- there is no torch fallback here.  It is not a device_loop.OneStreamLoop, which is
 replay-shaped (rows flow into a replay, a batch is sampled out of it).
@@ -68,6 +74,7 @@ class PpoLoopConfig:
     gae_lambda: Optional[float] = None  # None: the reference's estimator; else GAE(lambda), any horizon >= 1
     normalize_adv: bool = False        # GAE only: the batch's advantages to mean 0, std 1
     n_minibatches: int = 1             # K > 1: every epoch is a shuffled pass of K optimiser steps (ppo.PPOSolver)
+    bootstrap_time_limit: bool = False  # GAE only: bootstrap through episode ends that the time limit alone caused
 
 
 class PpoLoop:
@@ -82,6 +89,8 @@ class PpoLoop:
         self.gae = cfg.gae_lambda is not None
         if cfg.normalize_adv and not self.gae:
             raise ValueError("PpoLoopConfig.normalize_adv normalises GAE's advantages: set gae_lambda")
+        if cfg.bootstrap_time_limit and not self.gae:
+            raise ValueError("PpoLoopConfig.bootstrap_time_limit bootstraps GAE through time-limit ends: set gae_lambda")
         if self.gae and not 0.0 <= cfg.gae_lambda <= 1.0:
             raise ValueError(f"PpoLoopConfig.gae_lambda {cfg.gae_lambda}: None or 0..1")
         if self.gae and cfg.horizon < 1:
@@ -105,7 +114,8 @@ class PpoLoop:
                                f"{self.solver.impl_active!r} (impl={impl!r}); there is no torch fallback")
         self.actors = VecPpoActors(cfg.env, cfg.n_actors, cfg.horizon, seed=cfg.seed,
                                    max_episode_steps=self.max_episode_steps, device=self.device,
-                                   cap=cfg.horizon if self.gae else None)  # GAE: no carry
+                                   cap=cfg.horizon if self.gae else None,  # GAE: no carry
+                                   time_limit_bootstrap=bool(cfg.bootstrap_time_limit))
         if K > 1 and self.actors.N * self.actors.cap > MAX_SHUFFLE_ROWS:
             raise ValueError(f"PpoLoopConfig.n_minibatches {K}: the batch capacity n_actors * cap = "
                              f"{self.actors.N * self.actors.cap} is above the shuffle's {MAX_SHUFFLE_ROWS} rows")
