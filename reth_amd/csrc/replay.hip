@@ -386,18 +386,21 @@ int launch_copy(CopyArgs &a, hipStream_t s) {
     const int64_t nb = col.in_bytes;
     const uintptr_t al = reinterpret_cast<uintptr_t>(col.src) | reinterpret_cast<uintptr_t>(col.dst) |
                          (uintptr_t)col.src_stride | (uintptr_t)col.dst_stride;
-    if (nb <= kSmallRow) {
-      col.chunks = 0;
-      // plain copies of whole 4-byte words (a, r, done, Q heads): a lane per word
-      col.vec = col.conv == CONV_COPY && nb % 4 == 0 && al % 4 == 0;
-      blocks += ((col.vec ? a.n * (nb / 4) : a.n) + kCopyThreads - 1) / kCopyThreads;
-      continue;
-    }
+    // a frame-stack column is always chunked, however small its row: the one-lane-per-row
+    // branch of k_copy_rows has no CONV_STACK arm (one chunk covers a row of <= 64 bytes, and
+    // the chunk's `off + 16 <= nb` guard ends it)
     if (col.conv == CONV_STACK) {
       col.chunk_in = 16 * kCopyThreads;
       col.chunks = (nb + col.chunk_in - 1) / col.chunk_in;
       col.vec = 1;  // frame_bytes % 16 == 0 and 16-byte aligned store / output (checked at attach)
       blocks += a.n * col.chunks;
+      continue;
+    }
+    if (nb <= kSmallRow) {
+      col.chunks = 0;
+      // plain copies of whole 4-byte words (a, r, done, Q heads): a lane per word
+      col.vec = col.conv == CONV_COPY && nb % 4 == 0 && al % 4 == 0;
+      blocks += ((col.vec ? a.n * (nb / 4) : a.n) + kCopyThreads - 1) / kCopyThreads;
       continue;
     }
     if (col.conv == CONV_U8_F32_HWC) {

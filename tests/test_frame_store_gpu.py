@@ -72,10 +72,12 @@ def test_frame_store_loop_bit_identical_to_full_rows(dev, graph, bound):
 def test_frame_ids_loop_bit_identical(dev, graph):
     """frames in place (ApexConfig.frame_ids): the learner's batches are frame ids and conv1
     (forward, weight gradient, the target network's forward) reads the frames from the store --
-    every update bit-identical to the loop whose gather assembles the stacks"""
-    fs = _run(dev, True, graph, iters=150)
-    fi = _run(dev, True, graph, iters=150, frame_ids=True)
+    every update bit-identical to the loop whose gather assembles the stacks, the frame ring
+    (the "hard" size) wrapped in both"""
+    fs = _run(dev, True, graph, iters=230)
+    fi = _run(dev, True, graph, iters=230, frame_ids=True)
     assert fs["info"] == fi["info"] and fs["updates"] == fi["updates"] > 50
+    assert fs["head"] > fs["F"] and fi["head"] > fi["F"], "the frame ring must have wrapped in both runs"
     for x, y in zip(fs["cols"], fi["cols"]):
         assert torch.equal(x, y)
     assert torch.equal(fs["params"], fi["params"])
